@@ -2,6 +2,14 @@
 """Benchmark of the pairwise-ranking training hot path on MI355X.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes its outputs when
+--dump-outputs is given and prints the result line.  --full adds what else
+the benchmark measures, each in a pass of its own after the timed region: the
+per-kernel breakdown, SURVEY 8(d)'s batch, one drawn batch's row statistics
+(apply roofline, dedup-aware bytes), cfg5's scoring pass, the cfg1 NDCG@10
+check and the CPU baselines.
 
 Metric (BASELINE.json): BPR triplets/sec (d=64) + achieved HBM GB/s.
 Default workload = configs[1]: BPR-MF on a synthetic implicit-feedback graph,
@@ -324,6 +332,30 @@ def batch_stats(pairs, negs, groups, d, W):
     return out
 
 
+DUMP_TABLE_BYTES = 10 << 20   # per table; at most six tables (GBPR) + the loss: under 64 MB
+DUMP_SEED = 20261020
+
+
+def dump_outputs(eng, model, out_dir):
+    """What a caller of the timed path holds after its last step: every table
+    the step updates (rows and Adagrad accumulators, float32) and the loss it
+    accumulated since the start of the run (float64).  A table larger than
+    DUMP_TABLE_BYTES is written as a fixed sample of its rows: the row ids
+    depend only on the table's shape and DUMP_SEED."""
+    os.makedirs(out_dir, exist_ok=True)
+    names = ["user", "item", "acc_user", "acc_item"] + (["bias", "acc_bias"] if model == "gbpr" else [])
+    for name in names:
+        t = np.ascontiguousarray(eng.get_table(name), dtype=np.float32)
+        n_rows = t.shape[0]
+        keep = max(1, DUMP_TABLE_BYTES // max(1, t.nbytes // max(1, n_rows)))
+        if keep < n_rows:
+            rows = np.sort(np.random.RandomState(DUMP_SEED).choice(n_rows, size=keep, replace=False))
+            t = t[rows]
+        np.save(os.path.join(out_dir, name + ".npy"), t)
+        del t
+    np.save(os.path.join(out_dir, "loss.npy"), np.array([eng.take_loss()], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -331,6 +363,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--config", default="cfg2", choices=sorted(CONFIGS))
     ap.add_argument("--batch", type=int, default=0, help="pairs per GPU per step (0 = config)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the passes beside the headline figure: per-kernel breakdown, "
+                         "--secondary-batch, batch statistics, cfg5's score pass, cfg1 NDCG@10, "
+                         "CPU baselines (each can still be switched off by its own flag)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the tables and the loss the timed path left "
+                         "after its last step to DIR/<name>.npy (float32 / float64; tables larger "
+                         "than their share of 64 MB as a fixed seeded sample of rows)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--no-ndcg", action="store_true", help="skip the cfg1 NDCG@10 check")
@@ -601,9 +641,15 @@ def main():
         rem_ms, _ = eng.profile_read("step_remote")
         step_ms += rem_ms
 
+    if args.dump_outputs:   # before any later pass steps the tables again
+        if sharded and hasattr(step, "sync_state"):
+            step.sync_state()   # item-range ownership: gather the owners' accumulator rows
+        if rank == 0:
+            dump_outputs(eng, cfg["model"], args.dump_outputs)
+
     # per-kernel breakdown: a separate, untimed pass with every launch timed
     kernels = {}
-    if not args.no_profile:
+    if args.full and not args.no_profile:
         nb = min(args.steps, 50)
         eng.profile_reset()
         eng.set_option("profile_mask", 0xFFFFFFFF)
@@ -671,7 +717,7 @@ def main():
     # SURVEY 8(d)'s batch (65,536 pairs per GPU) on the same engine and graph
     secondary = None
     B2 = args.secondary_batch
-    if B2 and B2 != B and B2 <= len(indices):
+    if args.full and B2 and B2 != B and B2 <= len(indices):
         run(max(2, args.warmup // 2), B2)
         sync()
         eng.profile_reset()
@@ -699,11 +745,12 @@ def main():
     # one drawn batch's row multiplicities -> the apply + draw launch's and a
     # dedup-aware step's algorithmic bytes (batch_stats)
     st = None
-    try:
-        bp, bn, bg = eng.sample(B)
-        st = batch_stats(bp, bn, bg, d, W)
-    except Exception as ex:  # diagnostics only
-        log("batch stats failed: %r" % (ex,))
+    if args.full:
+        try:
+            bp, bn, bg = eng.sample(B)
+            st = batch_stats(bp, bn, bg, d, W)
+        except Exception as ex:  # diagnostics only
+            log("batch stats failed: %r" % (ex,))
 
     trip_per_step = B * W
     total_trip = trip_per_step * args.steps * world
@@ -799,7 +846,7 @@ def main():
         "kernels": kernels,
     }
     out["config"].update(dist_info)
-    if args.score_pass or args.config == "cfg5":
+    if args.score_pass or (args.full and args.config == "cfg5"):
         users = np.arange(u1 - u0, dtype=np.int32)
         eng.score_topk(users[:1024], 10)          # warm-up
         sync()
@@ -826,13 +873,13 @@ def main():
                              "kernel_ms_hip_events": tk_ms if tk_n else None,
                              "kernel_TFLOPs": (2.0 * (u1 - u0) * ni * d / (1e-3 * tk_ms) / 1e12)
                              if tk_n and tk_ms > 0 else None}
-    if rank == 0 and world == 1 and not args.no_ndcg:
+    if args.full and rank == 0 and world == 1 and not args.no_ndcg:
         try:
             out["ndcg10_vs_ref"] = ndcg_cfg1(local_rank)
         except Exception as ex:  # the bench line must still print
             log("cfg1 ndcg run failed: %r" % (ex,))
             out["ndcg10_vs_ref"] = None
-    if rank == 0 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and not args.no_cpu_baseline:
         # at N > 1 too (verdict r03): rank 0 times the same bounded sample on
         # its host cores after the timed region, on its own user shard, while
         # the other ranks wait at the closing barrier

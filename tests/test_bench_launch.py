@@ -62,6 +62,44 @@ def test_rank_count_mismatch_fails():
     assert r.returncode != 0
 
 
+class _FakeEngine:
+    """Tables as an engine's get_table returns them (float32), one loss."""
+
+    def __init__(self, tables, loss):
+        self.tables, self.loss = tables, loss
+
+    def get_table(self, name):
+        return self.tables[name]
+
+    def take_loss(self):
+        return self.loss
+
+
+def test_dump_outputs_writes_tables_and_fixed_row_sample(tmp_path, monkeypatch):
+    """--dump-outputs: every table of the model as float32 .npy and the loss
+    as float64; a table over its byte share is a row sample whose ids depend
+    only on its shape, so two runs (two builds) dump the same rows."""
+    import numpy as np
+    monkeypatch.setattr(bench, "DUMP_TABLE_BYTES", 64 * 16 * 4)   # 64 rows of d = 16
+    rng = np.random.RandomState(5)
+    tabs = {"user": rng.rand(1000, 16).astype(np.float32), "item": rng.rand(40, 16).astype(np.float32),
+            "acc_user": rng.rand(1000, 16).astype(np.float32), "acc_item": rng.rand(40, 16).astype(np.float32),
+            "bias": rng.rand(40).astype(np.float32), "acc_bias": rng.rand(40).astype(np.float32)}
+    for run in ("a", "b"):
+        bench.dump_outputs(_FakeEngine(tabs, 12.5), "gbpr", str(tmp_path / run))
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in list(tabs) + ["loss"]}
+    assert got["loss"].dtype == np.float64 and got["loss"].tolist() == [12.5]
+    for n in ("item", "acc_item", "bias", "acc_bias"):            # under the share: whole
+        assert got[n].dtype == np.float32 and np.array_equal(got[n], tabs[n])
+    rows = np.sort(np.random.RandomState(bench.DUMP_SEED).choice(1000, size=64, replace=False))
+    for n in ("user", "acc_user"):
+        assert got[n].shape == (64, 16) and np.array_equal(got[n], tabs[n][rows])
+        assert np.array_equal(got[n], np.load(str(tmp_path / "b" / (n + ".npy"))))
+    bench.dump_outputs(_FakeEngine(tabs, 0.0), "bpr", str(tmp_path / "c"))
+    assert sorted(os.listdir(str(tmp_path / "c"))) == ["acc_item.npy", "acc_user.npy", "item.npy", "loss.npy",
+                                                        "user.npy"]
+
+
 def test_epoch_order_charge():
     """bench.py charges only the epoch orders a timed region owes but did not
     compute on its clock (sorted batches)."""

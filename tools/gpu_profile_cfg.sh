@@ -10,7 +10,7 @@ TAG=$1; shift
 OUT=${GRAFT_REPO_ROOT:-$PWD}/gpurun_out/prof_$TAG
 mkdir -p $OUT
 A="--steps 100 --warmup 10 --no-cpu-baseline --no-ndcg --secondary-batch 0 $*"
-timeout -k 10 400 python bench.py $A > $OUT/bench.json 2> $OUT/bench.err || { echo "$TAG bench failed"; tail -20 $OUT/bench.err; exit 1; }
+timeout -k 10 400 python bench.py --full $A > $OUT/bench.json 2> $OUT/bench.err || { echo "$TAG bench failed"; tail -20 $OUT/bench.err; exit 1; }
 python -c "import json; d=json.load(open('$OUT/bench.json')); print('$TAG', d['value'], d['ms_per_step'], d['roofline']['frac'], d['roofline']['pmc_key'])"
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- python bench.py $A > $OUT/trace.log 2>&1 || { echo "$TAG trace pass failed"; tail -20 $OUT/trace.log; exit 1; }
 timeout -s KILL 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o run -- python bench.py $A --no-profile > $OUT/fetch.log 2>&1 || { echo "$TAG fetch pass failed"; tail -20 $OUT/fetch.log; exit 1; }

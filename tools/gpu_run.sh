@@ -50,7 +50,7 @@ step_bench() {
   IFS=';' read -ra SPECS <<< "${BENCH:-default:}"
   for spec in "${SPECS[@]}"; do
     name=${spec%%:*}; args=${spec#*:}
-    timeout -k 10 ${BENCH_LIMIT:-500} python bench.py $args > $OUT/bench_$name.json 2> $OUT/bench_$name.err \
+    timeout -k 10 ${BENCH_LIMIT:-500} python bench.py --full $args > $OUT/bench_$name.json 2> $OUT/bench_$name.err \
         || { tail -20 $OUT/bench_$name.err; die "bench $name failed"; }
     python - "$OUT/bench_$name.json" "$name" <<'PY'
 import json, sys
@@ -86,7 +86,7 @@ step_pmc() {
 
 step_ab() {
   local lib v o on oa
-  local ARGS=${AB_ARGS:---steps 200 --warmup 20 --no-cpu-baseline --no-ndcg --secondary-batch 0}
+  local ARGS=${AB_ARGS:---full --steps 200 --warmup 20 --no-cpu-baseline --no-ndcg --secondary-batch 0}
   IFS=';' read -ra OS <<< "${VARIANT_OPTS:-base:}"
   for lib in collaborativefilteringusingtensorflow_amd/build/libcf_engine.so \
              collaborativefilteringusingtensorflow_amd/build/variants/*/libcf_engine.so; do
