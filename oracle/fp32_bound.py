@@ -39,6 +39,10 @@ The CPU tests (tests/test_fp32_bound.py) check that the float32 oracle, the
 float32 oracle with every dedup-sum taken in a shuffled order and in
 reverse, and a float32 Kahan-free pairwise sum all stay inside E, and that
 dropping one occurrence of a hot row, or applying it twice, falls outside.
+
+``score_bound`` is the same analysis for the recommend step's scores
+(cf_oracle.predict); oracle/topk_check.py derives the near-tie rule of the
+top-k lists from it.
 """
 import numpy as np
 
@@ -65,6 +69,43 @@ def gamma(n):
 
 # the accumulators start at float32(0.1) on the engine, 0.1 in the float64 oracle
 ACC0_ERR = abs(float(np.float32(ACC_INIT)) - ACC_INIT)
+
+
+def score_bound(model, U, V, b, users):
+    """A-priori bound E >= |fp32 score - float64 score| of the recommend step
+    (= cf_oracle.predict), [len(users), n_items], for ANY float32 evaluation
+    of the score from the float32 tables U, V (and b):
+
+    * dot-product models (bpr, amf): d products and d - 1 adds in any order,
+      fused or not, plus one spare rounding for a sum split in two halves
+      that are added at the end (csrc/cf_eval.hip: lane halves, the
+      specialised-wave kernel's two accumulator chains):
+      gamma(d + 1) |U| |V|^T;
+    * gbpr and the tuple models (prigp, cplr): one more add for + b:
+      gamma(d + 2) (|U| |V|^T + |b|);
+    * cml, both forms -- the direct sum_k (u_k - v_k)^2 (score_kernel: one
+      rounding of each difference, squared, d terms: gamma(d + 2) |u - v|^2,
+      and |u - v|^2 <= |u|^2 + |v|^2 + 2 |U| |V|^T) and the fused kernels'
+      expansion 2 u.v - |v|^2 - |u|^2 (three sums of d terms, each with its
+      split-sum rounding, the doubling exact, two subtractions):
+      gamma(d + 4) (|u|^2 + |v|^2 + 2 |U| |V|^T).
+
+    Nothing in it is fitted to a measurement."""
+    U = np.asarray(U, dtype=np.float64)[np.asarray(users)]
+    V = np.asarray(V, dtype=np.float64)
+    d = U.shape[1]
+    M = np.abs(U) @ np.abs(V).T            # updated in place: [users, 1M items] is 1 GB a copy
+    if model == "cml":
+        M *= 2.0
+        M += np.sum(U * U, axis=1)[:, None]
+        M += np.sum(V * V, axis=1)[None, :]
+        M *= float(gamma(d + 4))
+    elif model in ("gbpr", "prigp", "cplr"):
+        M += np.abs(np.asarray(b, dtype=np.float64))[None, :]
+        M *= float(gamma(d + 2))
+    else:
+        M *= float(gamma(d + 1))
+    return M
 
 
 def zero_bounds(U, V, acc_exact=False):

@@ -30,6 +30,8 @@ import pytest
 
 from conftest import CML_TRAJ, assert_close
 from oracle import cf_oracle as O
+from oracle.fp32_bound import score_bound
+from oracle.topk_check import check_lists, check_values
 
 pytestmark = pytest.mark.gpu
 
@@ -244,8 +246,14 @@ def test_cml_final_top1000_materialised(fold1):
     U = e.get_table("user").astype(np.float64)
     V = e.get_table("item").astype(np.float64)
     users = np.nonzero(np.diff(fold1["test_indptr"]))[0].astype(np.int32)
-    idx = e.score_topk(users, 1000, exclude_train=True)
+    idx, val = e.score_topk(users, 1000, exclude_train=True, return_values=True)
     S = O.predict("cml", U, V, None, users)
     ref = O.recommend(S, fold1["train_indptr"], fold1["train_indices"], users, 1000)
-    _check_lists(idx, S, ref, atol=1e-5)
+    # values within the a-priori fp32 bound, mismatches only between near-ties
+    # no wider than twice it, and few of them (tests/test_gpu_topk.py)
+    E = score_bound("cml", U, V, None, users)
+    ip, ix = fold1["train_indptr"], fold1["train_indices"]
+    bad, total = check_lists(idx, S, ref, 1e-5, bound=E, excluded=[ix[ip[u]:ip[u + 1]] for u in users])
+    assert bad <= 0.05 * total, (bad, total)
+    check_values(val, idx, S, E, what="cml")
     e.close()

@@ -3,11 +3,22 @@ train-item exclusion and top-k order (descending, ties to the lower id, TF
 TopKV2) against the oracle's literal restatement.  Every test runs on both
 fused kernels (cf_set_option fused_variant: the sequential one and the
 software-pipelined one and, round 5, the specialised-wave one and the
-128-users-per-block one)."""
+128-users-per-block one).
+
+The returned VALUES are checked too: every value within the a-priori fp32
+bound E of the oracle's float64 score of the returned id
+(oracle/fp32_bound.py score_bound), NaN at every padded position.  A
+positional mismatch is allowed only between near-ties no wider than
+min(atol, 2 max E) (oracle/topk_check.py), no row may repeat an id or hold an
+excluded one, and at most MAX_MISMATCH of the compared positions may differ
+at all.  Tables whose scores are exact in float32, with no tolerance, and
+chosen arrival orders are in tests/test_gpu_topk_exact.py."""
 import numpy as np
 import pytest
 
 from oracle import cf_oracle as O
+from oracle.fp32_bound import score_bound
+from oracle.topk_check import check_lists, check_values
 
 pytestmark = pytest.mark.gpu
 
@@ -39,18 +50,24 @@ def setup(model, fold1, d, seed, bias=False, truncated=True):
     return e, U, V, b
 
 
-def check_lists(gpu_idx, scores, oracle_lists, atol):
-    """Exact order, except that adjacent near-ties (|ds| <= atol in the oracle's
-    fp64 scores) may swap because fp32 summation order differs."""
-    for r, (g, o) in enumerate(zip(gpu_idx, oracle_lists)):
-        g = [int(x) for x in g if x >= 0]
-        assert len(g) == len(o), r
-        if g == o:
-            continue
-        s = scores[r]
-        for a, b in zip(g, o):
-            if a != b:
-                assert abs(s[a] - s[b]) <= atol, (r, a, b, s[a], s[b])
+# A cap, not a measurement: on the CPU the share of the top 100's adjacent
+# fp64 gaps inside the derived near-tie width is 0.07-1.1 % at these shapes
+# (tests/test_fp32_bound.py::test_derived_tie_width_is_below_the_old_atol), so
+# a correct kernel cannot come near it; one that shuffles inside the list would
+MAX_MISMATCH = 0.05
+
+
+def train_rows(indptr, indices, users):
+    return [indices[indptr[u]:indptr[u + 1]] for u in users]
+
+
+def check_topk(model, out, S, E, ref, atol, excluded):
+    """The ids under the derived near-tie rule and the mismatch cap, the
+    values within E."""
+    idx, val = out
+    bad, total = check_lists(idx, S, ref, atol, bound=E, excluded=excluded)
+    assert bad <= MAX_MISMATCH * total, (bad, total)
+    check_values(val, idx, S, E, what=model)
 
 
 @pytest.mark.parametrize("path", [0, 1])          # auto (fused MFMA for k <= 28), materialised
@@ -61,12 +78,14 @@ def test_topk_matches_oracle(fold1, model, d, path):
     e.set_option("topk_path", path)
     tst_ip = fold1["test_indptr"]
     users = np.nonzero(np.diff(tst_ip))[0].astype(np.int32)
+    S = O.predict(model, U.astype(np.float64), V.astype(np.float64),
+                  None if b is None else b.astype(np.float64), users)
+    E = score_bound(model, U, V, b, users)
+    excl = train_rows(fold1["train_indptr"], fold1["train_indices"], users)
     for k in (1, 10, 28, 32, 100):
-        idx = e.score_topk(users, k, exclude_train=True)
-        S = O.predict(model, U.astype(np.float64), V.astype(np.float64),
-                      None if b is None else b.astype(np.float64), users)
+        out = e.score_topk(users, k, exclude_train=True, return_values=True)
         ref = O.recommend(S, fold1["train_indptr"], fold1["train_indices"], users, k)
-        check_lists(idx, S, ref, atol=1e-5)
+        check_topk(model, out, S, E, ref, 1e-5, excl)
     e.close()
 
 
@@ -79,8 +98,8 @@ def test_recommend_equals_literal_overfetch(fold1):
     ip, ix = fold1["train_indptr"], fold1["train_indices"]
     sets = [set(ix[ip[u]:ip[u + 1]].tolist()) for u in users]
     lit = O.recommend_literal(S, sets, 10)
-    idx = e.score_topk(users, 10)
-    check_lists(idx, S, lit, atol=1e-5)
+    out = e.score_topk(users, 10, return_values=True)
+    check_topk("bpr", out, S, score_bound("bpr", U, V, None, users), lit, 1e-5, train_rows(ip, ix, users))
     e.close()
 
 
@@ -161,16 +180,26 @@ def test_topk_item_mask_matches_oracle(fold1, model, d, path):
     users = np.arange(0, 943, 5, dtype=np.int32)
     S = O.predict(model, U.astype(np.float64), V.astype(np.float64),
                   None if b is None else b.astype(np.float64), users)
+    E = score_bound(model, U, V, b, users)
     both = _excl_csr(fold1, 943, mask, True)
     alone = _excl_csr(fold1, 943, mask, False)
+    x_both, x_alone = train_rows(both[0], both[1], users), train_rows(alone[0], alone[1], users)
+    x_train = train_rows(fold1["train_indptr"], fold1["train_indices"], users)
+
+    def ids_ok(idx, ref, excl):
+        bad, total = check_lists(idx, S, ref, 1e-5, bound=E, excluded=excl)
+        assert bad <= MAX_MISMATCH * total, (bad, total)
+
     for k in (10, 100):
-        idx = e.score_topk(users, k, exclude_train=True, item_mask=mask)
-        check_lists(idx, S, O.recommend(S, both[0], both[1], users, k), atol=1e-5)
-        idx = e.recommend(users, k, mask=mask)
-        check_lists(idx, S, O.recommend(S, alone[0], alone[1], users, k), atol=1e-5)
+        out = e.score_topk(users, k, exclude_train=True, item_mask=mask, return_values=True)
+        check_topk(model, out, S, E, O.recommend(S, both[0], both[1], users, k), 1e-5, x_both)
+        # the mask alone: cf_score_topk returns ids only, its _ex form the values too
+        ref = O.recommend(S, alone[0], alone[1], users, k)
+        ids_ok(e.recommend(users, k, mask=mask), ref, x_alone)
+        out = e.score_topk(users, k, exclude_train=False, item_mask=mask, return_values=True)
+        check_topk(model, out, S, E, ref, 1e-5, x_alone)
         idx = e.recommend(users, k)     # NULL: the reference's train filter
-        check_lists(idx, S, O.recommend(S, fold1["train_indptr"], fold1["train_indices"], users, k),
-                    atol=1e-5)
+        ids_ok(idx, O.recommend(S, fold1["train_indptr"], fold1["train_indices"], users, k), x_train)
     e.close()
 
 
@@ -212,9 +241,10 @@ def test_wide_k_gbpr_million_items(k):
     users = np.arange(0, nu, 4, dtype=np.int32)
     e.profile_reset()
     e.profile(True)
-    idx = e.score_topk(users, k)
+    out = e.score_topk(users, k, return_values=True)
     e.profile(False)
     assert e.profile_read("score")[1] == 0
     S = O.predict("gbpr", U.astype(np.float64), V.astype(np.float64), bb.astype(np.float64), users)
-    check_lists(idx, S, O.recommend(S, ip, ix, users, k), atol=2e-5)
+    E = score_bound("gbpr", U, V, bb, users)
+    check_topk("gbpr", out, S, E, O.recommend(S, ip, ix, users, k), 2e-5, train_rows(ip, ix, users))
     e.close()
