@@ -176,9 +176,10 @@ def test_det_fixed_point_range_guard(skewed_graph, how):
 @pytest.mark.parametrize("B,W", [(1 << 17, 1), (16384, 5)])
 def test_user_runs_equal_atomic_ranks(skewed_graph, B, W):
     """Sorted batches take each user's rank and count from the batch's runs
-    of consecutive pairs (StepArgs::user_runs) -- a plain store per run, one
-    atomic per wave only for a run crossing into another wave -- instead of
-    one returning count atomic per pair.  The ranks are a different
+    of consecutive pairs (StepArgs::user_runs) -- one non-returning atomic add
+    of the run's length per run, a returning one only for the wave's first and
+    last runs, which may continue in the neighbouring waves -- instead of one
+    returning count atomic per pair.  The ranks are a different
     permutation, so in deterministic mode (order-free fixed-point sums) the
     training must be BITWISE the same with user_runs on and off; at
     B = 2^17 on 40K users a batch has ~3.3 pairs per user, so many runs cross
