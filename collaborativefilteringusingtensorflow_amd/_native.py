@@ -126,6 +126,7 @@ SIGNATURES = {
     "cf_profile_enable": (ctypes.c_int, [_P, _I32]),
     "cf_profile_read": (ctypes.c_int, [_P, _I32, _PD, _PI64]),
     "cf_profile_reset": (ctypes.c_int, [_P]),
+    "cf_debug_live_bytes": (ctypes.c_int, [_PI64, _PI64]),
     "cf_ratings_load": (ctypes.c_int, [ctypes.c_char_p, _I64, _I64, _I32, ctypes.POINTER(_P), _PI64]),
     "cf_ratings_csr": (ctypes.c_int, [_P, _I32, ctypes.c_double, _PI64, _PI32, _PD, _PI64]),
     "cf_ratings_free": (ctypes.c_int, [_P]),

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -40,27 +41,71 @@ int fail(int code, const std::string& msg) {
         if (_r != CF_OK) return _r; \
     } while (0)
 
-template <class T>
-int dalloc(T** p, size_t n) {
-    *p = nullptr;
-    if (n == 0) return CF_OK;
-    hipError_t e = hipMalloc((void**)p, n * sizeof(T));
-    if (e != hipSuccess)
-        return fail(CF_ENOMEM, "hipMalloc(" + std::to_string(n * sizeof(T)) + " B): " +
-                                   hipGetErrorString(e));
-    return CF_OK;
-}
+// bytes held by live buffers of every engine in the process (cf_debug_live_bytes)
+std::atomic<int64_t> g_live_bytes[2];   // [0] device, [1] pinned host
 
-template <class T>
-void dfree(T*& p) {
-    if (p) (void)hipFree((void*)p);
-    p = nullptr;
-}
+// The one owner of a device (Pinned: pinned host) allocation; p and cap are in
+// elements.  It never synchronises: a caller that replaces a buffer a stream
+// may still use synchronises first.  A failed allocation clears HIP's sticky
+// error, so the next launch wrapper's hipGetLastError() does not report it.
+template <class T, bool Pinned = false>
+struct Buf {
+    T* p = nullptr;
+    size_t cap = 0;
+    Buf() = default;
+    Buf(Buf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+    Buf& operator=(Buf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
+    ~Buf() { release(); }
+    void release() {
+        if (p) (void)(Pinned ? hipHostFree((void*)p) : hipFree((void*)p));
+        g_live_bytes[Pinned] -= (int64_t)(cap * sizeof(T));
+        p = nullptr;
+        cap = 0;
+    }
+    int reset(size_t n, const char* what) {   // always a fresh buffer of exactly n elements
+        release();
+        if (n == 0) return CF_OK;
+        const hipError_t e = Pinned ? hipHostMalloc((void**)&p, n * sizeof(T), hipHostMallocDefault)
+                                    : hipMalloc((void**)&p, n * sizeof(T));
+        if (e != hipSuccess) {
+            p = nullptr;
+            (void)hipGetLastError();
+            return fail(CF_ENOMEM, std::string(Pinned ? "hipHostMalloc(" : "hipMalloc(") + what + ", " +
+                                       std::to_string(n * sizeof(T)) + " B): " + hipGetErrorString(e));
+        }
+        cap = n;
+        g_live_bytes[Pinned] += (int64_t)(n * sizeof(T));
+        return CF_OK;
+    }
+    int reserve(size_t n, const char* what) { return cap >= n ? CF_OK : reset(n, what); }
+    T* get() const { return p; }
+    operator T*() const { return p; }
+};
+template <class T> using DevBuf = Buf<T, false>;
+template <class T> using PinBuf = Buf<T, true>;
 
 }  // namespace
 
 // deterministic range flags kept per step (cf_engine::fx_bad)
 constexpr int kFxSlots = 1024;
+
+// where the device sampler stands (cf_engine::epoch / batch / sampler_B)
+struct SamplerPos {
+    int64_t epoch = 0, batch = 0;
+    int sampler_B = 0;
+};
+// a batch the engine holds between two ABI calls: its arguments, buffer set and size
+struct HeldBatch {
+    StepArgs args{};
+    int set = 0, B = 0;
+};
+// a batch drawn + counted ahead of its step, with the sampler position it was
+// drawn from (restored if the draw is dropped)
+struct DrawnAhead {
+    bool live = false;
+    HeldBatch b;
+    SamplerPos from;
+};
 
 struct cf_engine {
     cf_config cfg{};
@@ -69,34 +114,28 @@ struct cf_engine {
 
     // graph (HBM)
     int64_t nnz = 0;
-    int64_t* indptr = nullptr;
-    int32_t* indices = nullptr;
-    int4* pairs = nullptr;   // (u, i, row start, row length) per interaction
-    int4* pf_recs[2] = {nullptr, nullptr};   // prefetched pair records per buffer set (StepArgs::pf_out)
-    // speculative negative counts (StepArgs::spec_ph), per buffer set
-    int2* spec_ph_[2] = {nullptr, nullptr};
-    int* spec_n_[2] = {nullptr, nullptr};
+    DevBuf<int64_t> indptr;
+    DevBuf<int32_t> indices;
+    DevBuf<int4> pairs;   // (u, i, row start, row length) per interaction
     // cf_set_option "spec_neg": off by default since sorted batches (cfg2
     // 0.3541 -> 0.3511 ms/step off, three runs each, profiles/r05/ab/r05w_*:
     // psort's phantom zeroing costs 3 us, the fused draw no longer gains)
     int spec_neg = 0;
     // deterministic mode on the pos_sort path: fixed-point partials and the
     // users' int64 overflow accumulators (StepArgs::det_fx)
-    long long* slotP64 = nullptr;
-    unsigned long long* GU64 = nullptr;   // [hot_cap, d] compact rows of users past their slot cap
-    int32_t* hotU = nullptr;              // [n_users] a hot user's compact row (psort)
-    int* hot_n = nullptr;                 // rows handed out this batch
-    int64_t hot_cap = 0;
-    unsigned long long* GV64 = nullptr;
-    int fx_cap = 0;
-    int pf_cap = 0;
+    DevBuf<long long> slotP64;
+    DevBuf<unsigned long long> GU64;   // compact rows of users past their slot cap
+    DevBuf<int32_t> hotU;              // [n_users] a hot user's compact row (psort)
+    DevBuf<int> hot_n;                 // rows handed out this batch
+    DevBuf<unsigned long long> GV64;
+    int fx_cap = 0;                    // batch size slotP64 / GU64 hold (0: re-size them)
     int pair_prefetch = 0;   // measured slower at cfg2 (gradient launch +20 us, draw -2 us): off
-    unsigned long long* pos_set = nullptr;  // Pos(u) membership set of (u << 32 | i) keys
+    DevBuf<unsigned long long> pos_set;  // Pos(u) membership set of (u << 32 | i) keys
     uint64_t pos_mask = 0;
     int neg_check = 0;       // cf_set_option("neg_check"): 1 = Pos(u) set, 0 = CSR row scan
     int64_t nnz_set = 0;     // interactions the set was built from
-    int64_t* indptr_t = nullptr;
-    int32_t* indices_t = nullptr;
+    DevBuf<int64_t> indptr_t;
+    DevBuf<int32_t> indices_t;
     std::vector<int64_t> h_indptr;
     // sorted batches (round 5, cf_set_option "sorted_batches", default 1):
     // each batch's pairs in pair (CSR) order, so the draw reads its records
@@ -118,16 +157,13 @@ struct cf_engine {
     // count atomic per pair -- the runs measured even at cfg2 (prep_body)
     int user_runs = 0;
     struct EpochOrder {
-        int32_t* keys = nullptr;     // radix-sort path: [2 nnz]
-        int32_t* vals = nullptr;     // index form: [nnz] (counting) or [2 nnz] (radix sort)
-        void* tmp = nullptr;
-        size_t tmp_bytes = 0;
-        int64_t keys_cap = 0, vals_cap = 0;
+        DevBuf<int32_t> keys;        // radix-sort path: [2 nnz]
+        DevBuf<int32_t> vals;        // index form: [nnz] (counting) or [2 nnz] (radix sort)
+        DevBuf<char> tmp;
         int64_t epoch = -1;
         int B = 0;
         const int32_t* order = nullptr;
-        int4* recs = nullptr;        // records form (sorted_batches 1 / 2): the sorted pair records
-        int64_t recs_cap = 0;        // elements, like keys_cap / vals_cap
+        DevBuf<int4> recs;           // records form (sorted_batches 1 / 2): the sorted pair records
         const int4* recs_sorted = nullptr;
         bool with_recs = false;
         hipEvent_t ready = nullptr;
@@ -136,27 +172,28 @@ struct cf_engine {
     hipStream_t eo_stream = nullptr;
     hipEvent_t eo_mark = nullptr;
 
-    // tables
+    // tables: the engine's own buffers in enum cf_table order, and the ones in
+    // use -- an item-side table may be bound to caller memory (cf_bind_table),
+    // the item gradient too (cf_bind_item_grad); the engine never frees those
+    DevBuf<float> tab[6];
     float *U = nullptr, *V = nullptr, *b = nullptr;
     float *AU = nullptr, *AV = nullptr, *Ab = nullptr;
-    float *GU = nullptr, *GV = nullptr, *Gb = nullptr;
-    float *GV_own = nullptr, *Gb_own = nullptr;
+    DevBuf<float> GU, GV_own, Gb_own;
+    float *GV = nullptr, *Gb = nullptr;
     // amf_mode CF_AMF_APR: the batch's summed embedding-loss gradient of every
     // duplicated row (apr_embed_kernel), zero between steps; Δ = epsilon *
     // l2_normalize(row).  Rows seen once take Δ from their own pair.
-    float *GadvU = nullptr, *GadvV = nullptr;
+    DevBuf<float> GadvU, GadvV;
     // multi-rank (dense_item_apply): GadvV is the caller's buffer
     // (cf_bind_apr_item_grad), all-reduced between cf_step_local_apr_embed and
     // cf_step_local_grad so every item row's Δ comes from the global batch
     float* GadvV_bound = nullptr;
-    int32_t* cntU_[2] = {nullptr, nullptr};  // per-row occurrence counts (0 between steps)
-    int32_t* cntV_[2] = {nullptr, nullptr};
     // store-and-sum of duplicated rows: row r of a table owns the fixed slot
     // rows [r*cap, (r+1)*cap) (cf_set_option "slot_max" = item cap,
     // "slot_max_user" = user cap); rows above their cap use float atomics
-    float* slotU = nullptr;   // [n_users * capU, d]
-    float* slotV = nullptr;   // [n_items * capV, d]
-    float* slotVb = nullptr;  // [n_items * capV] item-bias gradient beside each slot row (GBPR / PLR)
+    DevBuf<float> slotU;   // [n_users * capU, d]
+    DevBuf<float> slotV;   // [n_items * capV, d]
+    DevBuf<float> slotVb;  // [n_items * capV] item-bias gradient beside each slot row (GBPR / PLR)
     int capU = 2, capV = 32;
     // user cap chosen at the first step from the batch's expected occurrences
     // per user (ensure_batch) until cf_set_option("slot_max_user") sets it
@@ -165,28 +202,25 @@ struct cf_engine {
     // 16 B per duplicated item occurrence + each pair's pre-update user row
     // (GBPR: its group blend row) stashed once (StepArgs::recV)
     int item_recs = 0;
-    int4* recV = nullptr;     // [n_items * capV]
-    int4* recVc = nullptr;    // deterministic mode: [B*(1+W)]
-    float *stashU = nullptr, *stashB = nullptr;   // [stash_cap, d]
-    int stash_cap = 0;
+    DevBuf<int4> recV;     // [n_items * capV]
+    DevBuf<int4> recVc;    // deterministic mode: [B*(1+W)]
+    DevBuf<float> stashU, stashB;   // [max(B, Bcap), d]
     // hot item rows (occurrences past capV) spread their float atomics over
     // GV and hot_rep - 1 extra copies (cf_set_option "hot_replicas")
-    float* GVrep = nullptr;   // [hot_rep - 1][n_items, d]
+    DevBuf<float> GVrep;   // [hot_rep - 1][n_items, d]
     int hot_rep = 1;
     // positive-sorted gradient (cf_set_option "pos_sort"): positives counted
     // in cntP, pairs visited in positive-item order, one partial row per
     // (gradient block, positive item) in slotP (StepArgs::cntP)
     int pos_sort = 2;                 // 0 off, 1 on, 2 auto: on for B >= kPsortAutoB
     int capP = 8;                     // partial rows per item (slot_max_pos); later ones add with atomics
-    int32_t* cntP_[2] = {nullptr, nullptr};
-    int2* offPN = nullptr;            // [n_items + 1] exclusive scans of (positives, negatives) per item
-    int32_t* srec = nullptr;          // [order_cap, psort_stride(n_neg)] sorted pair records
+    DevBuf<int2> offPN;               // [n_items + 1] exclusive scans of (positives, negatives) per item
+    DevBuf<int32_t> srec;             // [order_cap, psort_stride(n_neg)] sorted pair records
     int order_cap = 0;
-    float* slotP = nullptr;           // [order_cap / kPsortPPB + 1 + n_items, d] (StepArgs::slotP)
-    float* slotN = nullptr;           // [slotN_rows, d] compact negative slot rows (offN[j] + rank)
+    DevBuf<float> slotP;              // [order_cap / kPsortPPB + 1 + n_items, d] (StepArgs::slotP)
+    DevBuf<float> slotN;              // [slotN_rows, d] compact negative slot rows (offN[j] + rank)
     int64_t slotN_rows = 0;           // order_cap * n_neg, doubled when speculative counts can apply
-    void* psort_tmp = nullptr;
-    size_t psort_tmp_bytes = 0;
+    DevBuf<char> psort_tmp;
     bool slots_ready = false;
     // cf_set_option("pipeline") for cf_train_steps: 0 = three launches per
     // step (prep, grad, apply); 1 = apply(s) + prep(s+1) fused (two launches);
@@ -197,30 +231,32 @@ struct cf_engine {
     // batch: two buffer sets, so that the sampler of step s+1 runs on the side
     // stream while step s's gradient and apply kernels run on the main stream
     int Bcap = 0;
-    int32_t* occU_[2] = {nullptr, nullptr};
-    int32_t* occV_[2] = {nullptr, nullptr};
-    int32_t* rankU_[2] = {nullptr, nullptr};  // occurrence rank inside its row
-    int32_t* rankV_[2] = {nullptr, nullptr};
+    struct BatchSet {
+        DevBuf<int32_t> occU, occV;      // [Bcap * users / items per pair]
+        DevBuf<int32_t> rankU, rankV;    // occurrence rank inside its row
+        DevBuf<int32_t> cntU, cntV;      // per-row occurrence counts (0 between steps)
+        DevBuf<int32_t> cntP;            // pos_sort: positives per item
+        DevBuf<int2> spec_ph;            // speculative negative counts (StepArgs::spec_ph)
+        DevBuf<int> spec_n;
+        DevBuf<int4> pf_recs;            // prefetched pair records (StepArgs::pf_out)
+        hipEvent_t prep_done = nullptr, apply_done = nullptr;
+    } bs[2];
     int set = 0;
     hipStream_t side = nullptr;
-    hipEvent_t prep_done[2] = {nullptr, nullptr};
-    hipEvent_t apply_done[2] = {nullptr, nullptr};
-    double* loss_partial = nullptr;
-    double* loss = nullptr;   // [0] running accumulator, [1] per-call scratch
-    float* coefs = nullptr;   // [B, 2] CPLR tuple coefficients (cf_step_plr)
-    int coefs_cap = 0;
-    double* h_loss = nullptr; // pinned
+    DevBuf<double> loss_partial;
+    DevBuf<double> loss;      // [0] running accumulator, [1] per-call scratch
+    DevBuf<float> coefs;      // [B, 2] CPLR tuple coefficients (cf_step_plr)
+    PinBuf<double> h_loss;
     // deterministic fixed-point range flags (StepArgs::fx_bad), one word per
     // step since the last check_fx (step k of the call: word min(k, kFxSlots-1)),
     // so a failing call names its first bad step
-    int* fx_bad = nullptr;
-    int* h_fx_bad = nullptr;  // pinned [kFxSlots]
+    DevBuf<int> fx_bad;
+    PinBuf<int> h_fx_bad;     // [kFxSlots]
     int fx_step = 0;
-    int32_t* h_stage = nullptr;
-    size_t stage_cap = 0;
+    PinBuf<int32_t> h_stage;
     int tuple_stride = 0;            // cf_step_plr: ids read from tuples [B, width]
-    int32_t* d_bad = nullptr;        // device-batch range check (pack kernel)
-    int32_t* h_bad = nullptr;        // pinned
+    DevBuf<int32_t> d_bad;           // device-batch range check (pack kernel)
+    PinBuf<int32_t> h_bad;
     hipEvent_t stage_ev = nullptr;
 
     // device sampler position
@@ -233,51 +269,34 @@ struct cf_engine {
     int world = 1, rank = 0;
     int64_t shard_u0 = 0, shard_u1 = 0;
     std::vector<int64_t> h_bounds;
-    int64_t* bounds = nullptr;       // [world + 1] device
+    DevBuf<int64_t> bounds;          // [world + 1]
     bool group_source_global = false;
-    int32_t* xhist = nullptr;        // pack histogram [blocks][world]
-    size_t xhist_cap = 0;
-    int32_t* xcounts = nullptr;      // [world + 1] device
-    int32_t* h_xcounts = nullptr;    // pinned mirror
+    DevBuf<int32_t> xhist;           // pack histogram [blocks][world]
+    DevBuf<int32_t> xcounts;         // [world + 1]
+    PinBuf<int32_t> h_xcounts;       // its host mirror
     int32_t *x_send_ids = nullptr, *x_recv_ids = nullptr;             // bound (caller) buffers
-    int32_t* x_own = nullptr;        // [recv cap] served row applies it (first server, no local occurrence)
+    DevBuf<int32_t> x_own;           // [recv cap] served row applies it (first server, no local occurrence)
     float *x_rows = nullptr, *x_grads = nullptr, *x_serve_rows = nullptr, *x_serve_grads = nullptr;
     int64_t x_send_cap = 0, x_recv_cap = 0;
     int x_stage = 0;                 // 0 idle, 1 begun, 2 served, 3 grads done
     int x_part = 0;                  // split step: gradient parts done (1: local-member pairs)
     bool x_items_done = false;       // split step: the items' apply ran (cf_xchg_finish_items)
-    // the next exchange batch drawn ahead (cf_xchg_draw), taken by cf_xchg_adopt;
-    // send_ids holds two halves of send_cap ids, one per buffer set
-    bool x_pend = false;
-    StepArgs x_pend_args{};
-    int x_pend_set = 0, x_pend_B = 0, x_pend_sampler_B = 0;
-    int64_t x_pend_epoch = 0, x_pend_batch = 0;
-
-    // split local step (cf_step_local_grad / cf_step_local_apply): the step
-    // between its two halves, and a batch already drawn + counted by the
-    // previous apply launch (device sampler), with the sampler position it
-    // was drawn from (restored if the draw is discarded)
+    // batches held between two ABI calls: the exchange step in progress (xb)
+    // and the next one drawn ahead (x_pend: cf_xchg_draw, taken by
+    // cf_xchg_adopt; send_ids holds two halves of send_cap ids, one per buffer
+    // set); the split local step between its two halves (lg: cf_step_local_grad
+    // / cf_step_local_apply) and the batch the previous apply launch already
+    // drew + counted (pend), dropped by discard_pending
+    HeldBatch xb, lg;
+    DrawnAhead x_pend, pend;
     int lg_stage = 0;
-    StepArgs lg_args{};
-    int lg_set = 0, lg_B = 0;
     // the multi-rank item reduce in pieces (cf_set_option "item_pieces"):
     // cf_step_item_reduce(q, P) reduces item rows piece q; lg_pieces_left of
     // the current local step are still to come
     int item_pieces = 1;
     int lg_pieces_left = 0;
     bool lg_pieces_deferred = false;
-    bool pend = false;
-    StepArgs pend_args{};
-    int pend_set = 0, pend_B = 0;
-    int64_t pend_epoch = 0, pend_batch = 0;
-    int pend_sampler_B = 0;
-    StepArgs x_args{};
-    int x_set = 0;
-    int x_B = 0;
 
-    // tables bound to caller device memory (cf_bind_table): the engine's own
-    // buffer of table t while it is bound, else null
-    float* own_tab[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     // item occurrences of the last local gradient launch: the rows of the
     // bound item gradient that cf_clear_item_grad re-zeroes
     const int32_t* last_occV = nullptr;
@@ -288,21 +307,18 @@ struct cf_engine {
     // compact slots, no float atomics on duplicated rows (cf_det.hip)
     int det = 0;
     int64_t det_cap = 0;                 // occurrences the buffers below hold
-    int32_t *det_keys = nullptr, *det_vals = nullptr, *det_off = nullptr;
-    void* det_tmp = nullptr;
-    size_t det_tmp_bytes = 0;
-    float *slotUc = nullptr, *slotVc = nullptr, *slotVbc = nullptr;
-    float *hotP = nullptr, *hotPb = nullptr;   // sums of the 64-slot tiles inside one row
+    DevBuf<int32_t> det_keys, det_vals, det_off;
+    DevBuf<char> det_tmp;
+    DevBuf<float> slotUc, slotVc, slotVbc;
+    DevBuf<float> hotP, hotPb;   // sums of the 64-slot tiles inside one row
 
     // model state
     int phase = 0;
     bool need_clip_U = false, need_clip_V = false;
 
     // eval workspace
-    uint32_t* keys = nullptr;
-    size_t keys_cap = 0;
-    uint64_t* item_mask = nullptr;   // cf_score_topk's caller mask, one bit per item
-    int64_t mask_words = 0;
+    DevBuf<uint32_t> keys;
+    DevBuf<uint64_t> item_mask;   // cf_score_topk's caller mask, one bit per item
 
     int topk_path = 0;  // cf_set_option("topk_path")
     int fused_variant = 0;  // cf_set_option("fused_variant")
@@ -400,39 +416,35 @@ int ensure_slots(cf_engine* e) {
     if (e->slots_ready) return CF_OK;
     const cf_config& c = e->cfg;
     CF_HIP(hipStreamSynchronize(e->stream));
-    dfree(e->slotU);
-    dfree(e->slotV);
-    dfree(e->slotVb);
-    dfree(e->recV);
-    dfree(e->GVrep);
-    dfree(e->offPN);
-    for (int k = 0; k < 2; ++k) dfree(e->cntP_[k]);
-    if (e->psort_tmp) (void)hipFree(e->psort_tmp);
-    e->psort_tmp = nullptr;
+    // everything goes before anything comes back: the peak stays max(old, new)
+    e->slotU.release();
+    e->slotV.release();
+    e->slotVb.release();
+    e->recV.release();
+    e->GVrep.release();
+    e->offPN.release();
+    for (auto& s : e->bs) s.cntP.release();
+    e->psort_tmp.release();
     if (psort_possible(e)) {
-        CF_TRY(dalloc(&e->offPN, (size_t)c.n_items + 1));
-        for (int k = 0; k < 2; ++k) {
-            CF_TRY(dalloc(&e->cntP_[k], (size_t)c.n_items));
-            CF_HIP(hipMemsetAsync(e->cntP_[k], 0, (size_t)c.n_items * 4, e->stream));
+        CF_TRY(e->offPN.reset((size_t)c.n_items + 1, "offPN"));
+        for (auto& s : e->bs) {
+            CF_TRY(s.cntP.reset((size_t)c.n_items, "cntP"));
+            CF_HIP(hipMemsetAsync(s.cntP, 0, (size_t)c.n_items * 4, e->stream));
         }
-        e->psort_tmp_bytes = psort_scratch(c.n_items);
-        if (e->psort_tmp_bytes) {
-            hipError_t he = hipMalloc(&e->psort_tmp, e->psort_tmp_bytes);
-            if (he != hipSuccess) return fail(CF_ENOMEM, std::string("hipMalloc (psort scratch): ") + hipGetErrorString(he));
-        }
+        CF_TRY(e->psort_tmp.reset(psort_scratch(c.n_items), "psort scratch"));
     }
-    CF_TRY(dalloc(&e->slotU, (size_t)c.n_users * e->capU * c.n_factors));
+    CF_TRY(e->slotU.reset((size_t)c.n_users * e->capU * c.n_factors, "slotU"));
     if (!c.dense_item_apply || e->item_reduce == 1) {
         if (e->item_recs)
-            CF_TRY(dalloc(&e->recV, (size_t)c.n_items * e->capV));
+            CF_TRY(e->recV.reset((size_t)c.n_items * e->capV, "recV"));
         else
-            CF_TRY(dalloc(&e->slotV, (size_t)c.n_items * e->capV * c.n_factors));
-        if (has_bias(c)) CF_TRY(dalloc(&e->slotVb, (size_t)c.n_items * e->capV));
+            CF_TRY(e->slotV.reset((size_t)c.n_items * e->capV * c.n_factors, "slotV"));
+        if (has_bias(c)) CF_TRY(e->slotVb.reset((size_t)c.n_items * e->capV, "slotVb"));
     }
     if (!c.dense_item_apply) {
         if (e->hot_rep > 1) {
             const size_t n = (size_t)(e->hot_rep - 1) * c.n_items * c.n_factors;
-            CF_TRY(dalloc(&e->GVrep, n));
+            CF_TRY(e->GVrep.reset(n, "GVrep"));
             CF_HIP(hipMemsetAsync(e->GVrep, 0, n * sizeof(float), e->stream));
         }
     }
@@ -454,29 +466,26 @@ int ensure_det(cf_engine* e, int B, int B_step) {
         if (B > e->fx_cap) {
             CF_HIP(hipStreamSynchronize(e->stream));
             CF_HIP(hipStreamSynchronize(e->side));
-            dfree(e->slotP64);
-            CF_TRY(dalloc(&e->slotP64, ((size_t)B / kPsortPPB + 1 + (size_t)c.n_items) * c.n_factors));
+            CF_TRY(e->slotP64.reset(((size_t)B / kPsortPPB + 1 + (size_t)c.n_items) * c.n_factors, "slotP64"));
             // users past their slot cap: at most one per capU + 1 user
             // occurrences of the batch, each one compact int64 row (was one
             // row per user of the table: 512 MB at cfg2, round-3 ADVICE)
-            dfree(e->GU64);
             const int64_t hc = (int64_t)B * users_per_pair(c) / (e->capU + 1) + 1;
-            CF_TRY(dalloc(&e->GU64, (size_t)hc * c.n_factors));
+            CF_TRY(e->GU64.reset((size_t)hc * c.n_factors, "GU64"));
             CF_HIP(hipMemsetAsync(e->GU64, 0, (size_t)hc * c.n_factors * 8, e->stream));
-            e->hot_cap = hc;
             e->fx_cap = B;
         }
         if (!e->hotU) {
-            CF_TRY(dalloc(&e->hotU, (size_t)c.n_users));
-            CF_TRY(dalloc(&e->hot_n, 1));
+            CF_TRY(e->hotU.reset((size_t)c.n_users, "hotU"));
+            CF_TRY(e->hot_n.reset(1, "hot_n"));
             CF_HIP(hipMemsetAsync(e->hot_n, 0, sizeof(int), e->stream));
         }
         if (!e->GV64) {
-            CF_TRY(dalloc(&e->GV64, (size_t)c.n_items * c.n_factors));
+            CF_TRY(e->GV64.reset((size_t)c.n_items * c.n_factors, "GV64"));
             CF_HIP(hipMemsetAsync(e->GV64, 0, (size_t)c.n_items * c.n_factors * 8, e->stream));
         }
         if (!e->fx_bad) {
-            CF_TRY(dalloc(&e->fx_bad, (size_t)kFxSlots));
+            CF_TRY(e->fx_bad.reset((size_t)kFxSlots, "fx_bad"));
             CF_HIP(hipMemsetAsync(e->fx_bad, 0, kFxSlots * sizeof(int), e->stream));
             e->fx_step = 0;
         }
@@ -487,45 +496,40 @@ int ensure_det(cf_engine* e, int B, int B_step) {
     if (n <= e->det_cap && e->det_off) return CF_OK;
     CF_HIP(hipStreamSynchronize(e->stream));
     CF_HIP(hipStreamSynchronize(e->side));
-    dfree(e->det_keys); dfree(e->det_vals); dfree(e->det_off); dfree(e->slotUc); dfree(e->slotVc);
-    dfree(e->slotVbc);
-    dfree(e->recVc);
-    dfree(e->hotP);
-    dfree(e->hotPb);
-    if (e->det_tmp) (void)hipFree(e->det_tmp);
-    e->det_tmp = nullptr;
+    e->det_keys.release(); e->det_vals.release(); e->det_off.release();
+    e->slotUc.release(); e->slotVc.release(); e->slotVbc.release(); e->recVc.release();
+    e->hotP.release(); e->hotPb.release();
+    e->det_tmp.release();
     e->det_cap = 0;
     const int64_t rows = c.n_users + c.n_items;
-    CF_TRY(dalloc(&e->det_keys, (size_t)(2 * n)));
-    CF_TRY(dalloc(&e->det_vals, (size_t)(2 * n)));
-    CF_TRY(dalloc(&e->det_off, (size_t)rows));
-    CF_TRY(dalloc(&e->slotUc, (size_t)nU * c.n_factors));
+    CF_TRY(e->det_keys.reset((size_t)(2 * n), "det_keys"));
+    CF_TRY(e->det_vals.reset((size_t)(2 * n), "det_vals"));
+    CF_TRY(e->det_off.reset((size_t)rows, "det_off"));
+    CF_TRY(e->slotUc.reset((size_t)nU * c.n_factors, "slotUc"));
     if (e->item_recs)
-        CF_TRY(dalloc(&e->recVc, (size_t)nV));
+        CF_TRY(e->recVc.reset((size_t)nV, "recVc"));
     else
-        CF_TRY(dalloc(&e->slotVc, (size_t)nV * c.n_factors));
-    if (has_bias(c)) CF_TRY(dalloc(&e->slotVbc, (size_t)nV));
-    CF_TRY(dalloc(&e->hotP, (size_t)(n / kDetTile + 1) * c.n_factors));
-    CF_TRY(dalloc(&e->hotPb, (size_t)(n / kDetTile + 1)));
-    e->det_tmp_bytes = det_ranks_scratch(n, rows);
-    if (e->det_tmp_bytes) {
-        hipError_t he = hipMalloc(&e->det_tmp, e->det_tmp_bytes);
-        if (he != hipSuccess) return fail(CF_ENOMEM, std::string("hipMalloc (sort scratch): ") + hipGetErrorString(he));
-    }
+        CF_TRY(e->slotVc.reset((size_t)nV * c.n_factors, "slotVc"));
+    if (has_bias(c)) CF_TRY(e->slotVbc.reset((size_t)nV, "slotVbc"));
+    CF_TRY(e->hotP.reset((size_t)(n / kDetTile + 1) * c.n_factors, "hotP"));
+    CF_TRY(e->hotPb.reset((size_t)(n / kDetTile + 1), "hotPb"));
+    CF_TRY(e->det_tmp.reset(det_ranks_scratch(n, rows), "sort scratch"));
     e->det_cap = n;
     return CF_OK;
 }
 
 int ensure_stash(cf_engine* e, int B) {
-    if (!e->item_recs || B <= e->stash_cap) return CF_OK;
     const cf_config& c = e->cfg;
+    if (!e->item_recs || (size_t)B * c.n_factors <= e->stashU.cap) return CF_OK;
     CF_HIP(hipStreamSynchronize(e->stream));
     CF_HIP(hipStreamSynchronize(e->side));
-    dfree(e->stashU);
-    dfree(e->stashB);
-    CF_TRY(dalloc(&e->stashU, (size_t)B * c.n_factors));
-    if (c.model == CF_GBPR) CF_TRY(dalloc(&e->stashB, (size_t)B * c.n_factors));
-    e->stash_cap = B;
+    e->stashU.release();
+    e->stashB.release();
+    CF_TRY(e->stashU.reset((size_t)B * c.n_factors, "stashU"));
+    if (c.model == CF_GBPR && e->stashB.reset((size_t)B * c.n_factors, "stashB") != CF_OK) {
+        e->stashU.release();   // its size says what both hold
+        return CF_ENOMEM;
+    }
     return CF_OK;
 }
 
@@ -555,20 +559,17 @@ int ensure_batch(cf_engine* e, int B) {
     if (B <= e->Bcap) return CF_OK;
     CF_HIP(hipStreamSynchronize(e->stream));
     CF_HIP(hipStreamSynchronize(e->side));
-    dfree(e->loss_partial);
+    e->loss_partial.release();
     const size_t nU = (size_t)B * users_per_pair(e->cfg);
     const size_t nV = (size_t)B * items_per_pair(e->cfg);
-    for (int k = 0; k < 2; ++k) {
-        dfree(e->occU_[k]);
-        dfree(e->occV_[k]);
-        dfree(e->rankU_[k]);
-        dfree(e->rankV_[k]);
-        CF_TRY(dalloc(&e->occU_[k], nU));
-        CF_TRY(dalloc(&e->occV_[k], nV));
-        CF_TRY(dalloc(&e->rankU_[k], nU));
-        CF_TRY(dalloc(&e->rankV_[k], nV));
+    for (auto& s : e->bs) {
+        s.occU.release(); s.occV.release(); s.rankU.release(); s.rankV.release();
+        CF_TRY(s.occU.reset(nU, "occU"));
+        CF_TRY(s.occV.reset(nV, "occV"));
+        CF_TRY(s.rankU.reset(nU, "rankU"));
+        CF_TRY(s.rankV.reset(nV, "rankV"));
     }
-    CF_TRY(dalloc(&e->loss_partial, (size_t)grad_blocks_max(B)));
+    CF_TRY(e->loss_partial.reset((size_t)grad_blocks_max(B), "loss_partial"));
     e->Bcap = B;
     return CF_OK;
 }
@@ -603,35 +604,34 @@ int ensure_order(cf_engine* e, int B) {
         // spec_neg switched on after the allocation: widen the slots only
         CF_HIP(hipStreamSynchronize(e->stream));
         CF_HIP(hipStreamSynchronize(e->side));
-        dfree(e->slotN);
         e->slotN_rows = 0;
-        CF_TRY(dalloc(&e->slotN, (size_t)need * e->cfg.n_factors));
+        CF_TRY(e->slotN.reset((size_t)need * e->cfg.n_factors, "slotN"));
         e->slotN_rows = need;
         return CF_OK;
     }
     CF_HIP(hipStreamSynchronize(e->stream));
     CF_HIP(hipStreamSynchronize(e->side));
-    dfree(e->srec);
-    dfree(e->slotN);
+    e->srec.release();
+    e->slotN.release();
     e->slotN_rows = 0;
-    dfree(e->slotP);
-    for (int q = 0; q < 2; ++q) {
-        dfree(e->spec_ph_[q]);
-        dfree(e->spec_n_[q]);
+    e->slotP.release();
+    for (auto& s : e->bs) {
+        s.spec_ph.release();
+        s.spec_n.release();
     }
-    CF_TRY(dalloc(&e->srec, (size_t)std::max(B, e->Bcap) * psort_stride(e->cfg.n_neg)));
+    CF_TRY(e->srec.reset((size_t)std::max(B, e->Bcap) * psort_stride(e->cfg.n_neg), "srec"));
     // one partial row per (gradient block, positive item): row block + item
-    CF_TRY(dalloc(&e->slotP, ((size_t)std::max(B, e->Bcap) / kPsortPPB + 1 + (size_t)e->cfg.n_items) *
-                                 e->cfg.n_factors));
+    CF_TRY(e->slotP.reset(((size_t)std::max(B, e->Bcap) / kPsortPPB + 1 + (size_t)e->cfg.n_items) *
+                              e->cfg.n_factors, "slotP"));
     // compact negative slots offN[j] + rank (slotN_need)
     const int64_t nN = slotN_need(e, std::max(B, e->Bcap));
-    CF_TRY(dalloc(&e->slotN, (size_t)nN * e->cfg.n_factors));
+    CF_TRY(e->slotN.reset((size_t)nN * e->cfg.n_factors, "slotN"));
     e->slotN_rows = nN;
     // at most one phantom per negative (StepArgs::spec_ph)
-    for (int q = 0; q < 2; ++q) {
-        CF_TRY(dalloc(&e->spec_ph_[q], (size_t)std::max(B, e->Bcap) * e->cfg.n_neg));
-        CF_TRY(dalloc(&e->spec_n_[q], 1));
-        CF_HIP(hipMemsetAsync(e->spec_n_[q], 0, sizeof(int), e->stream));
+    for (auto& s : e->bs) {
+        CF_TRY(s.spec_ph.reset((size_t)std::max(B, e->Bcap) * e->cfg.n_neg, "spec_ph"));
+        CF_TRY(s.spec_n.reset(1, "spec_n"));
+        CF_HIP(hipMemsetAsync(s.spec_n, 0, sizeof(int), e->stream));
     }
     // in-range ids from the start (a given-up fused scatter leaves old records)
     CF_HIP(hipMemsetAsync(e->srec, 0, (size_t)std::max(B, e->Bcap) * psort_stride(e->cfg.n_neg) * 4, e->stream));
@@ -669,7 +669,7 @@ StepArgs base_step_args(cf_engine* e, int B, int k) {
     a.indices = e->indices;
     a.indptr_t = e->indptr_t;
     a.indices_t = e->indices_t;
-    a.pos_set = e->neg_check ? e->pos_set : nullptr;
+    a.pos_set = e->neg_check ? e->pos_set.p : nullptr;
     a.pos_mask = e->pos_mask;
     a.lane_draw = e->neg_check == 2 ? 1 : 0;
     a.U = e->U; a.AU = e->AU; a.GU = e->GU;
@@ -678,15 +678,15 @@ StepArgs base_step_args(cf_engine* e, int B, int k) {
     a.lr = c.lr;
     a.clip_norm = c.clip_norm;
     a.clip = c.model == CF_CML ? 1 : 0;
-    a.occU = e->occU_[k];
-    a.occV = e->occV_[k];
-    a.cntU = e->cntU_[k];
-    a.cntV = e->cntV_[k];
-    a.rankU = e->rankU_[k];
-    a.rankV = e->rankV_[k];
+    a.occU = e->bs[k].occU;
+    a.occV = e->bs[k].occV;
+    a.cntU = e->bs[k].cntU;
+    a.cntV = e->bs[k].cntV;
+    a.rankU = e->bs[k].rankU;
+    a.rankV = e->bs[k].rankV;
     a.slotU = e->slotU;
     a.slotV = e->slotV;
-    a.slotVb = (has_bias(c) && (e->slotV || e->recV) && e->bias_slots) ? e->slotVb : nullptr;
+    a.slotVb = (has_bias(c) && (e->slotV || e->recV) && e->bias_slots) ? e->slotVb.p : nullptr;
     a.capU = e->capU;
     a.capV = e->capV;
     a.GVrep = e->GVrep;
@@ -696,13 +696,13 @@ StepArgs base_step_args(cf_engine* e, int B, int k) {
     a.count_items = (!c.dense_item_apply || e->item_reduce) ? 1 : 0;
     a.items_grad_only = (c.dense_item_apply && e->item_reduce) ? 1 : 0;
     if (c.dense_item_apply && e->item_reduce == 2) a.capV = 0;  // duplicates: float atomics
-    const bool ps = psort_active(e, B) && e->cntP_[k] && e->srec && e->order_cap >= B;
+    const bool ps = psort_active(e, B) && e->bs[k].cntP && e->srec && e->order_cap >= B;
     if (e->det && !ps) {   // compact slots at off[row] + rank, no caps, no atomics
         a.offU = e->det_off;
         a.offV = e->det_off + c.n_users;
         a.slotU = e->slotUc;
         a.slotV = e->slotVc;
-        a.slotVb = has_bias(c) ? e->slotVbc : nullptr;
+        a.slotVb = has_bias(c) ? e->slotVbc.p : nullptr;
         a.capU = a.capV = 1 << 30;
         a.GVrep = nullptr;
         a.repV = 0;
@@ -717,7 +717,7 @@ StepArgs base_step_args(cf_engine* e, int B, int k) {
         a.stashB = e->stashB;
     }
     if (ps) {
-        a.cntP = e->cntP_[k];
+        a.cntP = e->bs[k].cntP;
         a.srec = e->srec;
         a.slotP = e->slotP;
         a.slotV = e->slotN;   // negatives: compact slots offN[j] + rank
@@ -726,8 +726,8 @@ StepArgs base_step_args(cf_engine* e, int B, int k) {
         // (every item row visited: a phantom holding rank 0 cannot hide an
         // item from an owner rule) -- the same test as apply_args
         if (a.count_items && spec_possible(e, B) && e->slotN_rows >= 2 * (int64_t)B * c.n_neg) {
-            a.spec_ph = e->spec_ph_[k];
-            a.spec_n = e->spec_n_[k];
+            a.spec_ph = e->bs[k].spec_ph;
+            a.spec_n = e->bs[k].spec_n;
         }
         if (e->det && e->slotP64 && e->fx_cap >= B && e->GU64 && e->GV64) {
             // deterministic: the fast path's launches, every sum in fixed point
@@ -803,13 +803,10 @@ EpochNeed epoch_need(const cf_engine* e, int B) {
 void free_epoch_orders(cf_engine* e) {
     (void)hipDeviceSynchronize();
     for (auto& o : e->eo) {
-        dfree(o.keys);
-        dfree(o.vals);
-        dfree(o.recs);
-        if (o.tmp) (void)hipFree(o.tmp);
-        o.tmp = nullptr;
-        o.tmp_bytes = 0;
-        o.keys_cap = o.vals_cap = o.recs_cap = 0;
+        o.keys.release();
+        o.vals.release();
+        o.recs.release();
+        o.tmp.release();
         o.epoch = -1;
         o.async = false;
         o.order = nullptr;
@@ -821,10 +818,10 @@ bool sorted_auto_fits(cf_engine* e, int B) {
     const EpochNeed n = epoch_need(e, B);
     double more = 0.0;   // what the two slots still have to allocate
     for (const auto& o : e->eo) {
-        if (o.keys_cap < n.keys) more += 4.0 * (double)n.keys;
-        if (o.vals_cap < n.vals) more += 4.0 * (double)n.vals;
-        if (o.recs_cap < n.recs) more += 16.0 * (double)n.recs;
-        if (o.tmp_bytes < n.tmp) more += (double)n.tmp;
+        if (o.keys.cap < (size_t)n.keys) more += 4.0 * (double)n.keys;
+        if (o.vals.cap < (size_t)n.vals) more += 4.0 * (double)n.vals;
+        if (o.recs.cap < (size_t)n.recs) more += 16.0 * (double)n.recs;
+        if (o.tmp.cap < n.tmp) more += (double)n.tmp;
     }
     if (more == 0.0) return true;
     size_t free_b = 0, total_b = 0;
@@ -835,17 +832,13 @@ bool sorted_auto_fits(cf_engine* e, int B) {
     return (double)free_b >= more + (double)e->sorted_reserve_mb * (double)(1 << 20);
 }
 
-// grow one buffer of an order slot (the device is synchronised first: the
+// re-size one buffer of an order slot that is too small (the device is synchronised first: the
 // old buffer may still be read by a draw or written by the other stream)
 template <typename T>
-int grow(T** p, int64_t* cap, int64_t need) {
-    if (*cap >= need) return CF_OK;
+int refit(DevBuf<T>& b, size_t need, const char* what) {
+    if (b.cap >= need) return CF_OK;
     CF_HIP(hipDeviceSynchronize());
-    dfree(*p);
-    *cap = 0;
-    CF_TRY(dalloc(p, (size_t)need));
-    *cap = need;
-    return CF_OK;
+    return b.reset(need, what);
 }
 
 // the order of (epoch, B) in slot k, enqueued on stream st
@@ -854,31 +847,23 @@ int compute_epoch_order(cf_engine* e, int k, int64_t epoch, int B, hipStream_t s
     const int64_t nnz = e->nnz;
     const bool wr = e->sorted_batches != 3;   // the records form
     const EpochNeed n = epoch_need(e, B);
-    CF_TRY(grow(&o.keys, &o.keys_cap, n.keys));
-    CF_TRY(grow(&o.vals, &o.vals_cap, n.vals));
-    CF_TRY(grow(&o.recs, &o.recs_cap, n.recs));
-    if (n.tmp > o.tmp_bytes) {
-        CF_HIP(hipDeviceSynchronize());
-        if (o.tmp) (void)hipFree(o.tmp);
-        o.tmp = nullptr;
-        o.tmp_bytes = 0;
-        hipError_t he = hipMalloc(&o.tmp, n.tmp);
-        if (he != hipSuccess) return fail(CF_ENOMEM, std::string("hipMalloc (epoch order scratch): ") + hipGetErrorString(he));
-        o.tmp_bytes = n.tmp;
-    }
+    CF_TRY(refit(o.keys, (size_t)n.keys, "epoch order keys"));
+    CF_TRY(refit(o.vals, (size_t)n.vals, "epoch order values"));
+    CF_TRY(refit(o.recs, (size_t)n.recs, "epoch order records"));
+    CF_TRY(refit(o.tmp, n.tmp, "epoch order scratch"));
     const PermKey pk = make_perm_key((uint64_t)nnz, e->cfg.seed, (uint64_t)epoch);
     {
         ProfScope ps(e, CF_K_EPOCH_ORDER, st);
         if (n.counting) {
-            CF_HIP(launch_epoch_count(pk, nnz, B, wr ? e->pairs : nullptr, wr ? o.recs : nullptr,
-                                      wr ? nullptr : o.vals, o.tmp, o.tmp_bytes, st));
-            o.recs_sorted = wr ? o.recs : nullptr;
-            o.order = wr ? nullptr : o.vals;
+            CF_HIP(launch_epoch_count(pk, nnz, B, wr ? e->pairs.p : nullptr, wr ? o.recs.p : nullptr,
+                                      wr ? nullptr : o.vals.p, o.tmp, o.tmp.cap, st));
+            o.recs_sorted = wr ? o.recs.p : nullptr;
+            o.order = wr ? nullptr : o.vals.p;
         } else if (wr) {
-            CF_HIP(launch_epoch_records(pk, nnz, B, e->pairs, o.keys, o.recs, o.tmp, o.tmp_bytes, &o.recs_sorted, st));
+            CF_HIP(launch_epoch_records(pk, nnz, B, e->pairs, o.keys, o.recs, o.tmp, o.tmp.cap, &o.recs_sorted, st));
             o.order = nullptr;
         } else {
-            CF_HIP(launch_epoch_order(pk, nnz, B, o.keys, o.vals, o.tmp, o.tmp_bytes, &o.order, st));
+            CF_HIP(launch_epoch_order(pk, nnz, B, o.keys, o.vals, o.tmp, o.tmp.cap, &o.order, st));
             o.recs_sorted = nullptr;
         }
         o.with_recs = wr;
@@ -1001,8 +986,8 @@ static int stage_device_batch(cf_engine* e, const int32_t* pairs, const int32_t*
     if (!is_device_ptr(negs) || (G > 0 && !is_device_ptr(groups)))
         return fail(CF_EINVAL, "a batch must be all host or all device memory");
     if (!e->d_bad) {
-        CF_TRY(dalloc(&e->d_bad, 1));
-        CF_HIP(hipHostMalloc((void**)&e->h_bad, sizeof(int32_t), hipHostMallocDefault));
+        CF_TRY(e->d_bad.reset(1, "d_bad"));
+        CF_TRY(e->h_bad.reset(1, "h_bad"));
     }
     PackArgs a{};
     a.u = pairs;
@@ -1018,8 +1003,8 @@ static int stage_device_batch(cf_engine* e, const int32_t* pairs, const int32_t*
     a.shard_u0 = e->shard_u0;
     a.shard_u1 = e->shard_u1;
     a.total_users = e->world > 1 ? e->h_bounds[e->world] : c.n_users;
-    a.occU = e->occU_[k];
-    a.occV = e->occV_[k];
+    a.occU = e->bs[k].occU;
+    a.occV = e->bs[k].occV;
     a.bad = e->d_bad;
     CF_HIP(hipMemsetAsync(e->d_bad, 0x7F, sizeof(int32_t), st));
     CF_HIP(launch_pack_batch(a, st));
@@ -1043,17 +1028,8 @@ int stage_host_batch(cf_engine* e, const int32_t* pairs, const int32_t* negs,
     const size_t js = e->tuple_stride ? (size_t)e->tuple_stride : (size_t)W;
     const size_t nU = (size_t)B * (1 + G), nV = (size_t)B * (1 + W);
     const size_t need = nU + nV;
-    if (need > e->stage_cap) {
-        if (e->h_stage) {
-            (void)hipEventSynchronize(e->stage_ev);
-            (void)hipHostFree(e->h_stage);
-            e->h_stage = nullptr;
-        }
-        CF_HIP(hipHostMalloc((void**)&e->h_stage, need * sizeof(int32_t), hipHostMallocDefault));
-        e->stage_cap = need;
-    } else {
-        CF_HIP(hipEventSynchronize(e->stage_ev));
-    }
+    CF_HIP(hipEventSynchronize(e->stage_ev));   // the previous batch's copies have left the buffer
+    CF_TRY(e->h_stage.reserve(need, "h_stage"));
     int32_t* su = e->h_stage;
     int32_t* sv = e->h_stage + nU;
     const int64_t nu = c.n_users, ni = c.n_items;
@@ -1082,8 +1058,8 @@ int stage_host_batch(cf_engine* e, const int32_t* pairs, const int32_t* negs,
             su[B + (size_t)p * G + k] = g;
         }
     }
-    CF_HIP(hipMemcpyAsync(e->occU_[k], su, nU * sizeof(int32_t), hipMemcpyHostToDevice, st));
-    CF_HIP(hipMemcpyAsync(e->occV_[k], sv, nV * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    CF_HIP(hipMemcpyAsync(e->bs[k].occU, su, nU * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    CF_HIP(hipMemcpyAsync(e->bs[k].occV, sv, nV * sizeof(int32_t), hipMemcpyHostToDevice, st));
     CF_HIP(hipEventRecord(e->stage_ev, st));
     return CF_OK;
 }
@@ -1127,7 +1103,7 @@ ApplyArgs apply_args(cf_engine* e, const StepArgs& a, int B, int k, double* loss
     p.slotP64 = a.slotP64;
     p.GU64 = a.GU64;
     p.hotU = a.hotU;
-    p.hot_n = a.det_fx ? e->hot_n : nullptr;
+    p.hot_n = a.det_fx ? e->hot_n.p : nullptr;
     p.GV64 = a.GV64;
     p.fx_bad = a.fx_bad;
     p.d = c.n_factors;
@@ -1175,17 +1151,17 @@ ApplyArgs apply_args(cf_engine* e, const StepArgs& a, int B, int k, double* loss
     p.count_items = a.count_items;
     p.items_grad_only = a.items_grad_only;
     if (a.items_grad_only && a.capV == 0) p.count_items = 0;  // item_reduce 2: nothing to reduce
-    p.occU = e->occU_[k];
-    p.rankU = e->rankU_[k];
+    p.occU = e->bs[k].occU;
+    p.rankU = e->bs[k].rankU;
     p.nU = (int64_t)B * users_per_pair(c);
-    p.occV = e->occV_[k];
-    p.rankV = e->rankV_[k];
+    p.occV = e->bs[k].occV;
+    p.rankV = e->bs[k].rankV;
     p.nV = (int64_t)B * items_per_pair(c);
     p.shard_u0 = e->shard_u0;
     p.slotU = a.slotU;
     p.slotV = a.slotV;
-    p.cntU = e->cntU_[k];
-    p.cntV = e->cntV_[k];
+    p.cntU = e->bs[k].cntU;
+    p.cntV = e->bs[k].cntV;
     p.U = e->U; p.AU = e->AU; p.GU = e->GU;
     p.V = e->V; p.AV = e->AV; p.GV = e->GV;
     p.b = a.train_bias ? e->b : nullptr;  // PRIGP keeps b fixed (prigp.py:145)
@@ -1219,7 +1195,7 @@ int det_ranks(cf_engine* e, const StepArgs& a) {
     const cf_config& c = e->cfg;
     const int64_t nU = (int64_t)a.B * users_per_pair(c), nV = (int64_t)a.B * items_per_pair(c);
     CF_HIP(launch_det_ranks(a.occU, nU, a.occV, nV, c.n_users, c.n_users + c.n_items, a.rankU, a.rankV,
-                            e->det_off, e->det_keys, e->det_vals, e->det_tmp, e->det_tmp_bytes, e->stream));
+                            e->det_off, e->det_keys, e->det_vals, e->det_tmp, e->det_tmp.cap, e->stream));
     return CF_OK;
 }
 
@@ -1266,7 +1242,7 @@ int psort(cf_engine* e, const StepArgs& a) {
         q.hotU = e->hotU;
         q.hot_n = e->hot_n;
     }
-    CF_HIP(launch_psort(q, e->psort_tmp, e->psort_tmp_bytes, e->stream));
+    CF_HIP(launch_psort(q, e->psort_tmp, e->psort_tmp.cap, e->stream));
     return CF_OK;
 }
 
@@ -1285,7 +1261,7 @@ int finish_step(cf_engine* e, const StepArgs& a, int B, int k, double* loss_acc,
         }
         ProfScope ps(e, CF_K_APPLY);
         CF_HIP(launch_apply(p, e->stream));
-        if (e->prep_side) CF_HIP(hipEventRecord(e->apply_done[k], e->stream));
+        if (e->prep_side) CF_HIP(hipEventRecord(e->bs[k].apply_done, e->stream));
         return pending_clips(e);
     }
     if (next && e->pipeline == 2) {
@@ -1299,7 +1275,7 @@ int finish_step(cf_engine* e, const StepArgs& a, int B, int k, double* loss_acc,
         CF_TRY(det_hot(e, a));
         ProfScope ps(e, CF_K_APPLY);
         CF_HIP(launch_apply(p, e->stream));
-        if (e->prep_side) CF_HIP(hipEventRecord(e->apply_done[k], e->stream));
+        if (e->prep_side) CF_HIP(hipEventRecord(e->bs[k].apply_done, e->stream));
         return pending_clips(e);
     }
     {
@@ -1314,7 +1290,7 @@ int finish_step(cf_engine* e, const StepArgs& a, int B, int k, double* loss_acc,
         ProfScope ps(e, CF_K_APPLY);
         CF_HIP(launch_apply(p, e->stream));
     }
-    if (e->prep_side) CF_HIP(hipEventRecord(e->apply_done[k], e->stream));
+    if (e->prep_side) CF_HIP(hipEventRecord(e->bs[k].apply_done, e->stream));
     return pending_clips(e);
 }
 
@@ -1331,12 +1307,12 @@ int run_step(cf_engine* e, int B, const int32_t* pairs, const int32_t* negs,
     e->set ^= 1;
     hipStream_t ps = e->prep_side ? e->side : e->stream;
     // set k was last used by step s-2: its apply must be done before reuse
-    if (e->prep_side) CF_HIP(hipStreamWaitEvent(ps, e->apply_done[k], 0));
+    if (e->prep_side) CF_HIP(hipStreamWaitEvent(ps, e->bs[k].apply_done, 0));
     StepArgs a;
     CF_TRY(begin_step(e, B, pairs, negs, groups, k, ps, &a));
     if (e->prep_side) {
-        CF_HIP(hipEventRecord(e->prep_done[k], ps));
-        CF_HIP(hipStreamWaitEvent(e->stream, e->prep_done[k], 0));
+        CF_HIP(hipEventRecord(e->bs[k].prep_done, ps));
+        CF_HIP(hipStreamWaitEvent(e->stream, e->bs[k].prep_done, 0));
     }
     return finish_step(e, a, B, k, loss_acc, nullptr);
 }
@@ -1347,7 +1323,7 @@ int run_steps_device(cf_engine* e, int B, int n, double* loss_acc) {
     if (n <= 0) return CF_OK;
     CF_TRY(ensure_batch(e, B));
     int k = e->set;
-    if (e->prep_side) CF_HIP(hipStreamWaitEvent(e->stream, e->apply_done[k], 0));
+    if (e->prep_side) CF_HIP(hipStreamWaitEvent(e->stream, e->bs[k].apply_done, 0));
     StepArgs a;
     CF_TRY(begin_step(e, B, nullptr, nullptr, nullptr, k, e->stream, &a));
     // the positive-sorted gradient launch of step s fetches step s+1's pair
@@ -1356,13 +1332,9 @@ int run_steps_device(cf_engine* e, int B, int n, double* loss_acc) {
     const bool pf = e->pair_prefetch && a.srec != nullptr && e->pipeline == 1 && !e->prep_side &&
                     a.pos_set == nullptr && a.order == nullptr &&
                     a.order_recs == nullptr;
-    if (pf && e->pf_cap < B) {
+    if (pf && e->bs[1].pf_recs.cap < (size_t)B) {   // set 1's comes last: both hold B
         CF_HIP(hipStreamSynchronize(e->stream));
-        for (int q = 0; q < 2; ++q) {
-            dfree(e->pf_recs[q]);
-            CF_TRY(dalloc(&e->pf_recs[q], (size_t)B));
-        }
-        e->pf_cap = B;
+        for (auto& s : e->bs) CF_TRY(s.pf_recs.reset((size_t)B, "pf_recs"));
     }
     for (int s = 0; s < n; ++s) {
         StepArgs nx{};
@@ -1372,11 +1344,11 @@ int run_steps_device(cf_engine* e, int B, int n, double* loss_acc) {
             CF_TRY(check_det_args(e, nx));
             CF_TRY(sampler_args(e, B, &nx));
             if (pf) {
-                a.pf_out = e->pf_recs[k ^ 1];
+                a.pf_out = e->bs[k ^ 1].pf_recs;
                 a.pf_slot_base = nx.slot_base;
                 a.pf_perm = nx.perm;
                 a.pf_B = B;
-                nx.pre_pairs = e->pf_recs[k ^ 1];
+                nx.pre_pairs = e->bs[k ^ 1].pf_recs;
             }
         }
         CF_TRY(finish_step(e, a, B, k, loss_acc, more ? &nx : nullptr));
@@ -1448,34 +1420,37 @@ int read_loss(cf_engine* e, int slot, double* out) {
 
 // drop a batch the previous apply launch drew ahead: clear its occurrence
 // counts and put the sampler back where that draw started
-int discard_pending(cf_engine* e) {
-    if (e->x_pend) {   // a drawn-ahead exchange batch: uncount it, rewind the sampler
-        const cf_config& c = e->cfg;
-        const StepArgs& a = e->x_pend_args;
-        const int64_t nU = (int64_t)e->x_pend_B * users_per_pair(c), nV = (int64_t)e->x_pend_B * items_per_pair(c);
-        if (a.count_users) CF_HIP(launch_uncount(a.occU, nU, a.cntU, e->stream));
-        if (a.count_items) CF_HIP(launch_uncount(a.occV, nV, a.cntV, e->stream));
-        if (a.count_items && a.cntP) CF_HIP(launch_uncount(a.occV, e->x_pend_B, a.cntP, e->stream));
-        e->epoch = e->x_pend_epoch;
-        e->batch = e->x_pend_batch;
-        e->sampler_B = e->x_pend_sampler_B;
-        e->set = e->x_pend_set;
-        e->x_pend = false;
-    }
-    if (!e->pend) return CF_OK;
+SamplerPos sampler_pos(const cf_engine* e) { return {e->epoch, e->batch, e->sampler_B}; }
+
+void rewind(cf_engine* e, const SamplerPos& p) {
+    e->epoch = p.epoch;
+    e->batch = p.batch;
+    e->sampler_B = p.sampler_B;
+}
+
+int drop(cf_engine* e, DrawnAhead& d) {
+    if (!d.live) return CF_OK;
     const cf_config& c = e->cfg;
-    const StepArgs& a = e->pend_args;
-    const int64_t nU = (int64_t)e->pend_B * users_per_pair(c), nV = (int64_t)e->pend_B * items_per_pair(c);
+    const StepArgs& a = d.b.args;
+    const int64_t nU = (int64_t)d.b.B * users_per_pair(c), nV = (int64_t)d.b.B * items_per_pair(c);
+    // speculative phantoms: local batches only -- an exchange batch is GBPR's,
+    // which never takes pos_sort (psort_possible), so its spec_n and cntP are
+    // null.  They come off first: each takes 1 from its item's count, and the
+    // item's real occurrences then store 0 (after that store the decrement
+    // would leave the count negative)
+    if (a.spec_n) CF_HIP(launch_uncount_spec(a.spec_ph, a.spec_n, a.cntV, e->stream));
     if (a.count_users) CF_HIP(launch_uncount(a.occU, nU, a.cntU, e->stream));
     if (a.count_items) CF_HIP(launch_uncount(a.occV, nV, a.cntV, e->stream));
-    if (a.count_items && a.cntP) CF_HIP(launch_uncount(a.occV, e->pend_B, a.cntP, e->stream));
-    if (a.spec_n) CF_HIP(launch_uncount_spec(a.spec_ph, a.spec_n, a.cntV, e->stream));
-    e->epoch = e->pend_epoch;
-    e->batch = e->pend_batch;
-    e->sampler_B = e->pend_sampler_B;
-    e->set = e->pend_set;
-    e->pend = false;
+    if (a.count_items && a.cntP) CF_HIP(launch_uncount(a.occV, d.b.B, a.cntP, e->stream));
+    rewind(e, d.from);
+    e->set = d.b.set;
+    d.live = false;
     return CF_OK;
+}
+
+int discard_pending(cf_engine* e) {
+    CF_TRY(drop(e, e->x_pend));   // the exchange batch was drawn last: its position first
+    return drop(e, e->pend);
 }
 
 // a user-sharded GBPR engine steps only through the group exchange
@@ -1527,15 +1502,11 @@ float** table_slot(cf_engine* e, int t) {
 int score_topk_fused(cf_engine* e, const int32_t* users, int n, int k, int exclude_train,
                      const uint64_t* item_mask, int32_t* idx_out, float* val_out) {
     const cf_config& c = e->cfg;
-    int32_t* d_users = nullptr;
-    int32_t* d_idx = nullptr;
-    float* d_val = nullptr;
-    int r = CF_OK;
-    if ((r = dalloc(&d_users, (size_t)n)) || (r = dalloc(&d_idx, (size_t)n * k)) ||
-        (val_out && (r = dalloc(&d_val, (size_t)n * k)))) {
-        dfree(d_users); dfree(d_idx); dfree(d_val);
-        return r;
-    }
+    DevBuf<int32_t> d_users, d_idx;
+    DevBuf<float> d_val;
+    CF_TRY(d_users.reset((size_t)n, "top-k users"));
+    CF_TRY(d_idx.reset((size_t)n * k, "top-k indices"));
+    if (val_out) CF_TRY(d_val.reset((size_t)n * k, "top-k values"));
     FusedTopkArgs f{};
     f.model = c.model == CF_PLR ? CF_GBPR : c.model;  // U.V^T + b (prigp.py:137, cplr_u.py:146)
     f.d = c.n_factors;
@@ -1561,7 +1532,9 @@ int score_topk_fused(cf_engine* e, const int32_t* users, int n, int k, int exclu
     // over the waves and printed (tools/score_ab.py)
     const size_t n_st = (size_t)((n + 63) / 64) * 8 * 16;
     std::vector<unsigned long long> h_st(n_st, 0ull);
-    if (he == hipSuccess) he = hipMalloc(&f.stamps, n_st * sizeof(unsigned long long));
+    DevBuf<unsigned long long> d_st;
+    CF_TRY(d_st.reset(n_st, "fused stamps"));
+    f.stamps = d_st;
     if (he == hipSuccess) he = hipMemsetAsync(f.stamps, 0, n_st * sizeof(unsigned long long), e->stream);
 #endif
     if (he == hipSuccess) {
@@ -1571,7 +1544,6 @@ int score_topk_fused(cf_engine* e, const int32_t* users, int n, int k, int exclu
     if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
 #ifdef CF_FUSED_STAMPS
     if (he == hipSuccess) he = hipMemcpy(h_st.data(), f.stamps, n_st * sizeof(unsigned long long), hipMemcpyDefault);
-    if (f.stamps) (void)hipFree(f.stamps);
     if (he == hipSuccess) {
         static const char* names[14] = {"stage", "bar1", "mfma", "cand_rest", "bar2", "tile_wait", "store",
                                         "compact", "bar3", "", "", "prefilter", "exact", ""};
@@ -1590,7 +1562,6 @@ int score_topk_fused(cf_engine* e, const int32_t* users, int n, int k, int exclu
     if (he == hipSuccess) he = hipMemcpy(idx_out, d_idx, (size_t)n * k * 4, hipMemcpyDefault);
     if (he == hipSuccess && val_out)
         he = hipMemcpy(val_out, d_val, (size_t)n * k * 4, hipMemcpyDefault);
-    dfree(d_users); dfree(d_idx); dfree(d_val);
     if (he != hipSuccess) return fail(CF_EHIP, std::string("cf_score_topk (fused): ") + hipGetErrorString(he));
     return CF_OK;
 }
@@ -1681,49 +1652,51 @@ int cf_create(const cf_config* cfg, cf_engine** out) {
     if (hipEventCreateWithFlags(&e->stage_ev, hipEventDisableTiming) != hipSuccess)
         return bail(fail(CF_EHIP, "hipEventCreate failed"));
     for (int k = 0; k < 2; ++k)
-        if (hipEventCreateWithFlags(&e->prep_done[k], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&e->apply_done[k], hipEventDisableTiming) != hipSuccess)
+        if (hipEventCreateWithFlags(&e->bs[k].prep_done, hipEventDisableTiming) != hipSuccess ||
+            hipEventCreateWithFlags(&e->bs[k].apply_done, hipEventDisableTiming) != hipSuccess)
             return bail(fail(CF_EHIP, "hipEventCreate failed"));
     (void)hipEventRecord(e->stage_ev, e->stream);
     const size_t ud = (size_t)c.n_users * c.n_factors, id = (size_t)c.n_items * c.n_factors;
-    if ((r = dalloc(&e->U, ud)) || (r = dalloc(&e->AU, ud)) || (r = dalloc(&e->GU, ud)) ||
-        (r = dalloc(&e->V, id)) || (r = dalloc(&e->AV, id)) || (r = dalloc(&e->GV_own, id)) ||
-        (r = dalloc(&e->cntU_[0], (size_t)c.n_users)) || (r = dalloc(&e->cntV_[0], (size_t)c.n_items)) ||
-        (r = dalloc(&e->cntU_[1], (size_t)c.n_users)) || (r = dalloc(&e->cntV_[1], (size_t)c.n_items)) ||
-        (r = dalloc(&e->loss, 2)))
+    DevBuf<float>* const tab = e->tab;
+    if ((r = tab[CF_TABLE_USER].reset(ud, "U")) || (r = tab[CF_TABLE_ACC_USER].reset(ud, "AU")) ||
+        (r = e->GU.reset(ud, "GU")) || (r = tab[CF_TABLE_ITEM].reset(id, "V")) ||
+        (r = tab[CF_TABLE_ACC_ITEM].reset(id, "AV")) || (r = e->GV_own.reset(id, "GV")))
         return bail(r);
+    for (auto& s : e->bs)
+        if ((r = s.cntU.reset((size_t)c.n_users, "cntU")) || (r = s.cntV.reset((size_t)c.n_items, "cntV")))
+            return bail(r);
+    if ((r = e->loss.reset(2, "loss"))) return bail(r);
     if (has_bias(c)) {
-        if ((r = dalloc(&e->b, (size_t)c.n_items)) || (r = dalloc(&e->Ab, (size_t)c.n_items)) ||
-            (r = dalloc(&e->Gb_own, (size_t)c.n_items)))
+        if ((r = tab[CF_TABLE_BIAS].reset((size_t)c.n_items, "b")) ||
+            (r = tab[CF_TABLE_ACC_BIAS].reset((size_t)c.n_items, "Ab")) ||
+            (r = e->Gb_own.reset((size_t)c.n_items, "Gb")))
             return bail(r);
     }
+    for (int t = 0; t < 6; ++t) *table_slot(e, t) = tab[t];
     e->GV = e->GV_own;
     e->Gb = e->Gb_own;
     e->shard_u1 = c.n_users;
     if (c.amf_mode == CF_AMF_APR) {
-        if ((r = dalloc(&e->GadvU, ud))) return bail(r);
+        if ((r = e->GadvU.reset(ud, "GadvU"))) return bail(r);
         if (hipMemsetAsync(e->GadvU, 0, ud * 4, e->stream) != hipSuccess)
             return bail(fail(CF_EHIP, "hipMemsetAsync failed"));
         if (!c.dense_item_apply) {   // multi-rank: the caller binds the item buffer
-            if ((r = dalloc(&e->GadvV, id))) return bail(r);
+            if ((r = e->GadvV.reset(id, "GadvV"))) return bail(r);
             if (hipMemsetAsync(e->GadvV, 0, id * 4, e->stream) != hipSuccess)
                 return bail(fail(CF_EHIP, "hipMemsetAsync failed"));
         }
     }
-    if (hipHostMalloc((void**)&e->h_loss, sizeof(double), hipHostMallocDefault) != hipSuccess)
-        return bail(fail(CF_ENOMEM, "pinned allocation failed"));
-    if (hipHostMalloc((void**)&e->h_fx_bad, kFxSlots * sizeof(int), hipHostMallocDefault) != hipSuccess)
-        return bail(fail(CF_ENOMEM, "pinned allocation failed"));
+    if ((r = e->h_loss.reset(1, "h_loss")) || (r = e->h_fx_bad.reset(kFxSlots, "h_fx_bad"))) return bail(r);
     *e->h_fx_bad = 0;
     hipStream_t s = e->stream;
     if (hipMemsetAsync(e->GU, 0, ud * 4, s) != hipSuccess ||
         hipMemsetAsync(e->GV, 0, id * 4, s) != hipSuccess ||
         hipMemsetAsync(e->U, 0, ud * 4, s) != hipSuccess ||
         hipMemsetAsync(e->V, 0, id * 4, s) != hipSuccess ||
-        hipMemsetAsync(e->cntU_[0], 0, (size_t)c.n_users * 4, s) != hipSuccess ||
-        hipMemsetAsync(e->cntV_[0], 0, (size_t)c.n_items * 4, s) != hipSuccess ||
-        hipMemsetAsync(e->cntU_[1], 0, (size_t)c.n_users * 4, s) != hipSuccess ||
-        hipMemsetAsync(e->cntV_[1], 0, (size_t)c.n_items * 4, s) != hipSuccess ||
+        hipMemsetAsync(e->bs[0].cntU, 0, (size_t)c.n_users * 4, s) != hipSuccess ||
+        hipMemsetAsync(e->bs[0].cntV, 0, (size_t)c.n_items * 4, s) != hipSuccess ||
+        hipMemsetAsync(e->bs[1].cntU, 0, (size_t)c.n_users * 4, s) != hipSuccess ||
+        hipMemsetAsync(e->bs[1].cntV, 0, (size_t)c.n_items * 4, s) != hipSuccess ||
         hipMemsetAsync(e->loss, 0, 2 * sizeof(double), s) != hipSuccess)
         return bail(fail(CF_EHIP, "hipMemsetAsync failed"));
     if (launch_fill(e->AU, (int64_t)ud, c.acc_init, s) != hipSuccess ||
@@ -1746,50 +1719,23 @@ int cf_destroy(cf_engine* e) {
     (void)hipSetDevice(e->cfg.device);
     if (e->stream) (void)hipStreamSynchronize(e->stream);
     if (e->side) (void)hipStreamSynchronize(e->side);
+    if (e->eo_stream) (void)hipStreamSynchronize(e->eo_stream);
     for (auto& v : e->ev)
         for (auto& pr : v) {
             (void)hipEventDestroy(pr.first);
             (void)hipEventDestroy(pr.second);
         }
     for (auto x : e->ev_pool) (void)hipEventDestroy(x);
-    for (int t = 0; t < 6; ++t)   // bound tables belong to the caller
-        if (e->own_tab[t]) *table_slot(e, t) = e->own_tab[t];
-    dfree(e->indptr); dfree(e->indices); dfree(e->pairs); dfree(e->indptr_t); dfree(e->indices_t);
-    dfree(e->pf_recs[0]); dfree(e->pf_recs[1]); dfree(e->slotP64); dfree(e->GU64); dfree(e->GV64); dfree(e->fx_bad);
-    dfree(e->hotU); dfree(e->hot_n);
-    for (auto& o : e->eo) {
-        dfree(o.keys);
-        dfree(o.vals);
-        dfree(o.recs);
-        if (o.tmp) (void)hipFree(o.tmp);
+    // (a bound table or item gradient is the caller's: the engine's own
+    // buffers stayed in tab[] / GV_own / Gb_own, which free themselves)
+    for (auto& o : e->eo)
         if (o.ready) (void)hipEventDestroy(o.ready);
-    }
     if (e->eo_mark) (void)hipEventDestroy(e->eo_mark);
     if (e->eo_stream) (void)hipStreamDestroy(e->eo_stream);
-    dfree(e->pos_set);
-    dfree(e->U); dfree(e->V); dfree(e->b); dfree(e->AU); dfree(e->AV); dfree(e->Ab);
-    dfree(e->GU); dfree(e->GV_own); dfree(e->Gb_own); dfree(e->GadvU); dfree(e->GadvV);
-    for (int k = 0; k < 2; ++k) {
-        dfree(e->cntU_[k]); dfree(e->cntV_[k]); dfree(e->occU_[k]); dfree(e->occV_[k]);
-        dfree(e->rankU_[k]); dfree(e->rankV_[k]);
-        if (e->prep_done[k]) (void)hipEventDestroy(e->prep_done[k]);
-        if (e->apply_done[k]) (void)hipEventDestroy(e->apply_done[k]);
+    for (auto& s : e->bs) {
+        if (s.prep_done) (void)hipEventDestroy(s.prep_done);
+        if (s.apply_done) (void)hipEventDestroy(s.apply_done);
     }
-    dfree(e->loss_partial); dfree(e->loss); dfree(e->keys); dfree(e->item_mask);
-    dfree(e->slotU); dfree(e->slotV); dfree(e->slotVb); dfree(e->GVrep); dfree(e->x_own); dfree(e->coefs);
-    dfree(e->bounds); dfree(e->xhist); dfree(e->xcounts);
-    dfree(e->det_keys); dfree(e->det_vals); dfree(e->det_off); dfree(e->slotUc); dfree(e->slotVc);
-    dfree(e->slotVbc); dfree(e->recV); dfree(e->recVc); dfree(e->stashU); dfree(e->stashB);
-    dfree(e->hotP); dfree(e->hotPb);
-    dfree(e->slotP); dfree(e->offPN); dfree(e->srec); dfree(e->slotN); dfree(e->cntP_[0]); dfree(e->cntP_[1]);
-    if (e->psort_tmp) (void)hipFree(e->psort_tmp);
-    if (e->det_tmp) (void)hipFree(e->det_tmp);
-    if (e->h_xcounts) (void)hipHostFree(e->h_xcounts);
-    if (e->h_loss) (void)hipHostFree(e->h_loss);
-    if (e->h_fx_bad) (void)hipHostFree(e->h_fx_bad);
-    if (e->h_stage) (void)hipHostFree(e->h_stage);
-    if (e->h_bad) (void)hipHostFree(e->h_bad);
-    dfree(e->d_bad);
     if (e->stage_ev) (void)hipEventDestroy(e->stage_ev);
     if (e->own_stream && e->stream) (void)hipStreamDestroy(e->stream);
     if (e->side) (void)hipStreamDestroy(e->side);
@@ -1821,11 +1767,10 @@ int cf_synchronize(cf_engine* e) {
 
 // the Pos(u) set of the current interactions (neg_check = 1), built on demand
 int build_pos_set(cf_engine* e) {
-    dfree(e->pos_set);
     const int64_t nnz = e->nnz_set;
     uint64_t cap = 1024;   // load factor <= 1/2
     while (cap < 2 * (uint64_t)nnz) cap <<= 1;
-    CF_TRY(dalloc(&e->pos_set, (size_t)cap));
+    CF_TRY(e->pos_set.reset((size_t)cap, "pos_set"));
     e->pos_mask = cap - 1;
     CF_HIP(launch_build_pos_set(e->pairs, nnz, e->pos_set, e->pos_mask, e->stream));
     return CF_OK;
@@ -1857,12 +1802,12 @@ int cf_set_interactions(cf_engine* e, const int64_t* indptr, const int32_t* indi
     if (e->eo_stream) CF_HIP(hipStreamSynchronize(e->eo_stream));
     for (auto& o : e->eo) o.epoch = -1;
     e->sorted_auto_off = false;   // sorted_auto_fits decides again for the new nnz
-    dfree(e->indptr); dfree(e->indices); dfree(e->pairs); dfree(e->indptr_t); dfree(e->indices_t);
-    dfree(e->pos_set);
-    CF_TRY(dalloc(&e->indptr, (size_t)c.n_users + 1));
-    CF_TRY(dalloc(&e->indices, (size_t)nnz + 4));   // + 4: the draw's 16-B row loads never leave it
+    e->indptr.release(); e->indices.release(); e->pairs.release();
+    e->indptr_t.release(); e->indices_t.release(); e->pos_set.release();
+    CF_TRY(e->indptr.reset((size_t)c.n_users + 1, "indptr"));
+    CF_TRY(e->indices.reset((size_t)nnz + 4, "indices"));   // + 4: the draw's 16-B row loads never leave it
     CF_HIP(hipMemsetAsync(e->indices + nnz, 0xFF, 16, e->stream));
-    CF_TRY(dalloc(&e->pairs, (size_t)nnz));
+    CF_TRY(e->pairs.reset((size_t)nnz, "pairs"));
     CF_HIP(hipMemcpyAsync(e->indptr, indptr, ((size_t)c.n_users + 1) * 8, hipMemcpyHostToDevice, e->stream));
     CF_HIP(hipMemcpyAsync(e->indices, indices, (size_t)nnz * 4, hipMemcpyHostToDevice, e->stream));
     CF_HIP(launch_build_pairs(e->indptr, e->indices, c.n_users, e->pairs, e->stream));
@@ -1877,8 +1822,8 @@ int cf_set_interactions(cf_engine* e, const int64_t* indptr, const int32_t* indi
         std::vector<int64_t> fill(tp.begin(), tp.end() - 1);
         for (int64_t u = 0; u < c.n_users; ++u)
             for (int64_t k = indptr[u]; k < indptr[u + 1]; ++k) tu[fill[indices[k]]++] = (int32_t)u;
-        CF_TRY(dalloc(&e->indptr_t, (size_t)c.n_items + 1));
-        CF_TRY(dalloc(&e->indices_t, (size_t)nnz));
+        CF_TRY(e->indptr_t.reset((size_t)c.n_items + 1, "indptr_t"));
+        CF_TRY(e->indices_t.reset((size_t)nnz, "indices_t"));
         CF_HIP(hipMemcpyAsync(e->indptr_t, tp.data(), tp.size() * 8, hipMemcpyHostToDevice, e->stream));
         CF_HIP(hipMemcpyAsync(e->indices_t, tu.data(), tu.size() * 4, hipMemcpyHostToDevice, e->stream));
         CF_HIP(hipStreamSynchronize(e->stream));  // host vectors go out of scope
@@ -2007,11 +1952,7 @@ int cf_step_plr(cf_engine* e, const int32_t* tuples, int32_t width, const float*
     if (c.plr_kind == CF_PLR_CPLR && !coefs) return fail(CF_EINVAL, "CPLR needs coefs [B, 2]");
     if (c.plr_kind == CF_PLR_CPLR) {
         CF_HIP(hipStreamSynchronize(e->stream));  // the previous step may still read the buffer
-        if (B > e->coefs_cap) {
-            dfree(e->coefs);
-            CF_TRY(dalloc(&e->coefs, (size_t)B * 2));
-            e->coefs_cap = B;
-        }
+        CF_TRY(e->coefs.reserve((size_t)B * 2, "coefs"));
         CF_HIP(hipMemcpy(e->coefs, coefs, (size_t)B * 2 * sizeof(float), hipMemcpyDefault));
     }
     double* acc = loss_out ? e->loss + 1 : e->loss;
@@ -2089,13 +2030,13 @@ int cf_sample(cf_engine* e, int32_t B, int32_t* pairs, int32_t* negs, int32_t* g
     a.count_users = 0;
     a.count_items = 0;
     hipStream_t ps = e->prep_side ? e->side : e->stream;
-    if (e->prep_side) CF_HIP(hipStreamWaitEvent(ps, e->apply_done[k], 0));
+    if (e->prep_side) CF_HIP(hipStreamWaitEvent(ps, e->bs[k].apply_done, 0));
     CF_HIP(launch_prep(a, ps));
     const size_t nU = (size_t)B * (1 + G), nV = (size_t)B * (1 + W);
     std::vector<int32_t> hu(nU), hv(nV);
     CF_HIP(hipStreamSynchronize(ps));
-    CF_HIP(hipMemcpy(hu.data(), e->occU_[k], nU * 4, hipMemcpyDeviceToHost));
-    CF_HIP(hipMemcpy(hv.data(), e->occV_[k], nV * 4, hipMemcpyDeviceToHost));
+    CF_HIP(hipMemcpy(hu.data(), e->bs[k].occU, nU * 4, hipMemcpyDeviceToHost));
+    CF_HIP(hipMemcpy(hv.data(), e->bs[k].occV, nV * 4, hipMemcpyDeviceToHost));
     for (int p = 0; p < B; ++p) {
         pairs[2 * p] = hu[p];
         pairs[2 * p + 1] = hv[p];
@@ -2111,23 +2052,15 @@ int cf_sample(cf_engine* e, int32_t B, int32_t* pairs, int32_t* negs, int32_t* g
 
 int cf_get_sampler_state(cf_engine* e, int64_t* epoch, int64_t* batch) {
     if (!e) return fail(CF_EINVAL, "null engine");
-    if (e->x_pend) {  // an exchange batch drawn ahead is not consumed yet
-        if (epoch) *epoch = e->x_pend_epoch;
-        if (batch) *batch = e->x_pend_batch;
-        return CF_OK;
-    }
-    if (e->pend) {  // a batch drawn ahead is not consumed yet
-        if (epoch) *epoch = e->pend_epoch;
-        if (batch) *batch = e->pend_batch;
-        return CF_OK;
-    }
-    if (epoch) *epoch = e->epoch;
-    if (batch) *batch = e->batch;
+    // a batch drawn ahead is not consumed yet
+    const SamplerPos p = e->x_pend.live ? e->x_pend.from : e->pend.live ? e->pend.from : sampler_pos(e);
+    if (epoch) *epoch = p.epoch;
+    if (batch) *batch = p.batch;
     return CF_OK;
 }
 
 int cf_set_sampler_state(cf_engine* e, int64_t epoch, int64_t batch) {
-    if (e && e->pend) CF_TRY(discard_pending(e));
+    if (e && e->pend.live) CF_TRY(discard_pending(e));
     if (!e) return fail(CF_EINVAL, "null engine");
     if (epoch < 0 || batch < 0) return fail(CF_EINVAL, "negative sampler state");
     e->epoch = epoch;
@@ -2191,16 +2124,29 @@ int cf_bind_apr_item_grad(cf_engine* e, void* ptr, int64_t n) {
     return CF_OK;
 }
 
+// the next local batch of B pairs, for the buffer set after k: the sampler
+// position it is drawn from and its arguments go into e->pend, which is live
+// once the caller's launch has drawn + counted it.  When the sampler fails,
+// pend.from is already written (pend is not live, so nothing reads it) and
+// pend.b is not
+static int stage_ahead(cf_engine* e, int B, int k) {
+    StepArgs nx = base_step_args(e, B, k ^ 1);
+    e->pend.from = sampler_pos(e);
+    CF_TRY(sampler_args(e, B, &nx));
+    e->pend.b = {nx, k ^ 1, B};
+    return CF_OK;
+}
+
 // the split step's batch: drawn + counted by the previous apply launch, or
 // drawn / packed now
 static int local_batch(cf_engine* e, int32_t B, const int32_t* pairs, const int32_t* negs,
                        const int32_t* groups, StepArgs* a, int* k) {
-    if (e->pend && (pairs || e->pend_B != B)) CF_TRY(discard_pending(e));
+    if (e->pend.live && (pairs || e->pend.b.B != B)) CF_TRY(discard_pending(e));
     CF_TRY(ensure_batch(e, B));
-    if (e->pend) {
-        *a = e->pend_args;
-        *k = e->pend_set;
-        e->pend = false;
+    if (e->pend.live) {
+        *a = e->pend.b.args;
+        *k = e->pend.b.set;
+        e->pend.live = false;
     } else {
         *k = e->set;
         e->set ^= 1;
@@ -2224,9 +2170,7 @@ int cf_step_local_apr_embed(cf_engine* e, int32_t B, const int32_t* pairs, const
         ProfScope ps(e, CF_K_STEP);
         CF_HIP(launch_apr_embed(a, e->stream));
     }
-    e->lg_args = a;
-    e->lg_set = k;
-    e->lg_B = B;
+    e->lg = {a, k, B};
     e->lg_stage = 3;   // the caller all-reduces the bound buffer, then cf_step_local_grad
     return CF_OK;
 }
@@ -2240,10 +2184,10 @@ int cf_step_local_grad(cf_engine* e, int32_t B, const int32_t* pairs, const int3
     StepArgs a;
     int k;
     if (e->lg_stage == 3) {   // after cf_step_local_apr_embed + the caller's all-reduce
-        if (pairs || negs || groups || B != e->lg_B)
+        if (pairs || negs || groups || B != e->lg.B)
             return fail(CF_EINVAL, "after cf_step_local_apr_embed pass the same B and no batch");
-        a = e->lg_args;
-        k = e->lg_set;
+        a = e->lg.args;
+        k = e->lg.set;
         a.apr_embed_done = 1;
         e->lg_stage = 0;
     } else {
@@ -2279,9 +2223,7 @@ int cf_step_local_grad(cf_engine* e, int32_t B, const int32_t* pairs, const int3
             CF_HIP(launch_apply(p, e->stream));
         }
     }
-    e->lg_args = a;
-    e->lg_set = k;
-    e->lg_B = B;
+    e->lg = {a, k, B};
     e->lg_stage = 1;
     return CF_OK;
 }
@@ -2311,7 +2253,7 @@ int cf_step_item_reduce(cf_engine* e, int32_t piece) {
     // dense pos_sort apply): every piece is already complete
     if (!e->lg_pieces_deferred) return CF_OK;
     if (piece != P - e->lg_pieces_left) return fail(CF_ESTATE, "item-reduce pieces run in order 0 .. item_pieces-1");
-    ApplyArgs p = apply_args(e, e->lg_args, e->lg_B, e->lg_set, nullptr);
+    ApplyArgs p = apply_args(e, e->lg.args, e->lg.B, e->lg.set, nullptr);
     p.count_users = 0;
     piece_rows(e->cfg.n_items, piece, P, &p.item_r0, &p.item_r1);
     if (p.item_r1 > p.item_r0) {
@@ -2328,26 +2270,19 @@ int cf_step_local_apply(cf_engine* e, int32_t next_B) {
     if (e->lg_pieces_left > 0)
         return fail(CF_ESTATE, "cf_step_item_reduce pieces of this step are still pending");
     if (next_B < 0) return fail(CF_EINVAL, "next_B must be >= 0");
-    const int k = e->lg_set;
-    ApplyArgs p = apply_args(e, e->lg_args, e->lg_B, k, e->loss);
+    const int k = e->lg.set;
+    ApplyArgs p = apply_args(e, e->lg.args, e->lg.B, k, e->loss);
     if (p.items_grad_only) p.count_items = 0;  // reduced in cf_step_local_grad
     e->lg_stage = 0;
     e->lg_done_set = k;
     if (next_B > 0 && next_B <= e->Bcap && e->prep_side == 0) {
         // draw + count the next batch in the same launch (other buffer set)
-        StepArgs nx = base_step_args(e, next_B, k ^ 1);
-        e->pend_epoch = e->epoch;
-        e->pend_batch = e->batch;
-        e->pend_sampler_B = e->sampler_B;
-        CF_TRY(sampler_args(e, next_B, &nx));
+        CF_TRY(stage_ahead(e, next_B, k));
         {
             ProfScope ps(e, CF_K_APPLY_PREP);
-            CF_HIP(launch_apply_prep(p, nx, e->stream));
+            CF_HIP(launch_apply_prep(p, e->pend.b.args, e->stream));
         }
-        e->pend = true;
-        e->pend_args = nx;
-        e->pend_set = k ^ 1;
-        e->pend_B = next_B;
+        e->pend.live = true;
         e->set = k;  // the set after the pending one
     } else {
         ProfScope ps(e, CF_K_APPLY);
@@ -2362,22 +2297,15 @@ int cf_step_local_draw(cf_engine* e, int32_t B) {
     CF_TRY(check_not_xchg(e));
     if (e->lg_stage != 0 || e->lg_done_set < 0)
         return fail(CF_ESTATE, "cf_step_local_draw follows cf_step_local_apply");
-    if (e->pend) return fail(CF_ESTATE, "the next batch is already drawn");
+    if (e->pend.live) return fail(CF_ESTATE, "the next batch is already drawn");
     if (B < 1 || B > e->Bcap) return fail(CF_EINVAL, "B must be in [1, the largest batch stepped so far]");
     const int k = e->lg_done_set;
-    StepArgs nx = base_step_args(e, B, k ^ 1);
-    e->pend_epoch = e->epoch;
-    e->pend_batch = e->batch;
-    e->pend_sampler_B = e->sampler_B;
-    CF_TRY(sampler_args(e, B, &nx));
+    CF_TRY(stage_ahead(e, B, k));
     {
         ProfScope ps(e, CF_K_SAMPLE);
-        CF_HIP(launch_prep(nx, e->stream));
+        CF_HIP(launch_prep(e->pend.b.args, e->stream));
     }
-    e->pend = true;
-    e->pend_args = nx;
-    e->pend_set = k ^ 1;
-    e->pend_B = B;
+    e->pend.live = true;
     e->set = k;
     return CF_OK;
 }
@@ -2418,11 +2346,10 @@ int cf_bind_table(cf_engine* e, int32_t t, void* ptr, int64_t n) {
     CF_TRY(discard_pending(e));
     CF_HIP(hipStreamSynchronize(e->stream));
     if (!ptr) {
-        if (e->own_tab[t]) {
-            CF_HIP(hipMemcpyAsync(e->own_tab[t], *slot, (size_t)want * 4, hipMemcpyDeviceToDevice, e->stream));
+        if (*slot != e->tab[t].p) {   // bound: the values come home to the engine's own buffer
+            CF_HIP(hipMemcpyAsync(e->tab[t], *slot, (size_t)want * 4, hipMemcpyDeviceToDevice, e->stream));
             CF_HIP(hipStreamSynchronize(e->stream));
-            *slot = e->own_tab[t];
-            e->own_tab[t] = nullptr;
+            *slot = e->tab[t];
         }
         return CF_OK;
     }
@@ -2433,8 +2360,7 @@ int cf_bind_table(cf_engine* e, int32_t t, void* ptr, int64_t n) {
     if ((float*)ptr == *slot) return CF_OK;
     CF_HIP(hipMemcpyAsync(ptr, *slot, (size_t)want * 4, hipMemcpyDeviceToDevice, e->stream));
     CF_HIP(hipStreamSynchronize(e->stream));
-    if (!e->own_tab[t]) e->own_tab[t] = *slot;
-    *slot = (float*)ptr;
+    *slot = (float*)ptr;   // tab[t] keeps the engine's own buffer
     (void)c;
     return CF_OK;
 }
@@ -2537,12 +2463,11 @@ int cf_set_shard(cf_engine* e, int32_t world, int32_t rank, const int64_t* bound
     e->shard_u0 = bounds[rank];
     e->shard_u1 = bounds[rank + 1];
     e->h_bounds.assign(bounds, bounds + world + 1);
-    dfree(e->bounds);
-    dfree(e->xcounts);
-    CF_TRY(dalloc(&e->bounds, (size_t)world + 1));
-    CF_TRY(dalloc(&e->xcounts, (size_t)world + 1));
-    if (!e->h_xcounts)
-        CF_HIP(hipHostMalloc((void**)&e->h_xcounts, 65 * sizeof(int32_t), hipHostMallocDefault));
+    e->bounds.release();
+    e->xcounts.release();
+    CF_TRY(e->bounds.reset((size_t)world + 1, "bounds"));
+    CF_TRY(e->xcounts.reset((size_t)world + 1, "xcounts"));
+    CF_TRY(e->h_xcounts.reserve(65, "h_xcounts"));
     CF_HIP(hipMemcpy(e->bounds, bounds, ((size_t)world + 1) * 8, hipMemcpyHostToDevice));
     return CF_OK;
 }
@@ -2560,10 +2485,10 @@ int cf_set_group_source(cf_engine* e, const int64_t* indptr_t, const int32_t* in
     for (int64_t k = 0; k < nnz; ++k)
         if (indices_t[k] < 0 || indices_t[k] >= nu) return fail(CF_EINVAL, "user id out of range");
     CF_HIP(hipStreamSynchronize(e->stream));
-    dfree(e->indptr_t);
-    dfree(e->indices_t);
-    CF_TRY(dalloc(&e->indptr_t, (size_t)c.n_items + 1));
-    CF_TRY(dalloc(&e->indices_t, (size_t)nnz));
+    e->indptr_t.release();
+    e->indices_t.release();
+    CF_TRY(e->indptr_t.reset((size_t)c.n_items + 1, "indptr_t"));
+    CF_TRY(e->indices_t.reset((size_t)nnz, "indices_t"));
     CF_HIP(hipMemcpy(e->indptr_t, indptr_t, ((size_t)c.n_items + 1) * 8, hipMemcpyHostToDevice));
     CF_HIP(hipMemcpy(e->indices_t, indices_t, (size_t)nnz * 4, hipMemcpyHostToDevice));
     e->group_source_global = true;
@@ -2592,8 +2517,7 @@ int cf_bind_exchange(cf_engine* e, void* send_ids, void* rows, void* grads, int6
     e->x_recv_ids = (int32_t*)recv_ids;
     e->x_serve_rows = (float*)serve_rows;
     e->x_serve_grads = (float*)serve_grads;
-    dfree(e->x_own);
-    CF_TRY(dalloc(&e->x_own, (size_t)(recv_cap > 0 ? recv_cap : 1)));
+    CF_TRY(e->x_own.reset((size_t)(recv_cap > 0 ? recv_cap : 1), "x_own"));
     e->x_recv_cap = recv_cap;
     return CF_OK;
 }
@@ -2621,17 +2545,15 @@ static int xchg_stage(cf_engine* e, int32_t B, const int32_t* pairs, const int32
     CF_TRY(ensure_batch(e, B));
     CF_TRY(begin_step(e, B, pairs, negs, groups, k, e->stream, a));
     const size_t nblk = (size_t)(n + kBlock - 1) / kBlock;
-    if (nblk * (size_t)e->world > e->xhist_cap) {
+    if (nblk * (size_t)e->world > e->xhist.cap) {
         CF_HIP(hipStreamSynchronize(e->stream));
-        dfree(e->xhist);
-        CF_TRY(dalloc(&e->xhist, nblk * (size_t)e->world));
-        e->xhist_cap = nblk * (size_t)e->world;
+        CF_TRY(e->xhist.reset(nblk * (size_t)e->world, "xhist"));
     }
     XchgArgs x{};
     x.n = n;
     x.world = e->world;
     x.bounds = e->bounds;
-    x.occ = e->occU_[k] + B;
+    x.occ = e->bs[k].occU + B;
     x.hist = e->xhist;
     x.counts = e->xcounts;
     x.send_ids = e->x_send_ids + (int64_t)half * e->x_send_cap;
@@ -2652,9 +2574,7 @@ int cf_xchg_begin(cf_engine* e, int32_t B, const int32_t* pairs, const int32_t* 
                           e->stream));
     CF_HIP(hipStreamSynchronize(e->stream));
     for (int r = 0; r < e->world; ++r) send_counts_out[r] = e->h_xcounts[r];
-    e->x_args = a;
-    e->x_set = k;
-    e->x_B = B;
+    e->xb = {a, k, B};
     e->x_stage = 1;
     e->x_part = 0;
     e->x_items_done = false;
@@ -2667,41 +2587,33 @@ int cf_xchg_draw(cf_engine* e, int32_t B, void* send_counts_dev, int32_t* half_o
     if (c.model != CF_GBPR || !c.dense_item_apply || e->h_bounds.empty() || !e->group_source_global)
         return fail(CF_ESTATE, "the group exchange needs GBPR, dense_item_apply=1, cf_set_shard and cf_set_group_source");
     if (e->det) return fail(CF_ESTATE, "deterministic mode does not cover the GBPR group exchange");
-    if (e->x_pend) return fail(CF_ESTATE, "an exchange batch is already drawn (cf_xchg_adopt takes it)");
+    if (e->x_pend.live) return fail(CF_ESTATE, "an exchange batch is already drawn (cf_xchg_adopt takes it)");
     if (!half_out) return fail(CF_EINVAL, "null half_out");
     CF_TRY(check_device_ptr(send_counts_dev, "send_counts_dev"));
     const int k = e->set;
-    const int64_t ep = e->epoch, bt = e->batch;
-    const int sb = e->sampler_B;
+    e->x_pend.from = sampler_pos(e);   // read only once the batch is live
     e->set ^= 1;
     StepArgs a;
     CF_TRY(xchg_stage(e, B, nullptr, nullptr, nullptr, k, k, &a));
     CF_HIP(hipMemcpyAsync((int32_t*)send_counts_dev + (int64_t)k * e->world, e->xcounts,
                           (size_t)e->world * 4, hipMemcpyDeviceToDevice, e->stream));
-    e->x_pend = true;
-    e->x_pend_args = a;
-    e->x_pend_set = k;
-    e->x_pend_B = B;
-    e->x_pend_epoch = ep;
-    e->x_pend_batch = bt;
-    e->x_pend_sampler_B = sb;
+    e->x_pend.b = {a, k, B};
+    e->x_pend.live = true;
     *half_out = k;
     return CF_OK;
 }
 
 int cf_xchg_adopt(cf_engine* e, int32_t B) {
     CF_TRY(check_xchg(e, 0));
-    if (!e->x_pend) return fail(CF_EAGAIN, "no exchange batch drawn ahead (cf_xchg_draw)");
-    if (e->x_pend_B != B) {   // drawn at another batch size: drop it (uncount, rewind the sampler)
-        const int drawn = e->x_pend_B;
+    if (!e->x_pend.live) return fail(CF_EAGAIN, "no exchange batch drawn ahead (cf_xchg_draw)");
+    if (e->x_pend.b.B != B) {   // drawn at another batch size: drop it (uncount, rewind the sampler)
+        const int drawn = e->x_pend.b.B;
         CF_TRY(discard_pending(e));
         return fail(CF_EAGAIN, "the batch drawn ahead has B=" + std::to_string(drawn) + ", not " +
                                    std::to_string(B) + ": discarded, draw again");
     }
-    e->x_args = e->x_pend_args;
-    e->x_set = e->x_pend_set;
-    e->x_B = e->x_pend_B;
-    e->x_pend = false;
+    e->xb = e->x_pend.b;
+    e->x_pend.live = false;
     e->x_stage = 1;
     e->x_part = 0;
     e->x_items_done = false;
@@ -2711,7 +2623,7 @@ int cf_xchg_adopt(cf_engine* e, int32_t B) {
 int cf_xchg_serve(cf_engine* e, int64_t n_recv) {
     CF_TRY(check_xchg(e, 1));
     if (n_recv < 0 || n_recv > e->x_recv_cap) return fail(CF_EINVAL, "n_recv exceeds the bound receive capacity");
-    CF_HIP(launch_xchg_serve(e->x_recv_ids, n_recv, e->shard_u0, e->cntU_[e->x_set], e->x_own, e->U,
+    CF_HIP(launch_xchg_serve(e->x_recv_ids, n_recv, e->shard_u0, e->bs[e->xb.set].cntU, e->x_own, e->U,
                              e->x_serve_rows,
                              e->cfg.n_factors, e->stream));
     e->x_stage = 2;
@@ -2721,13 +2633,13 @@ int cf_xchg_serve(cf_engine* e, int64_t n_recv) {
 int cf_xchg_grad(cf_engine* e) {
     CF_TRY(check_xchg(e, 2));
     if (e->x_part != 0) return fail(CF_ESTATE, "a split gradient (cf_xchg_grad_part) is in progress");
-    const StepArgs& a = e->x_args;
+    const StepArgs& a = e->xb.args;
     {
         ProfScope ps(e, CF_K_STEP);
         CF_HIP(launch_grad(a, e->stream));
     }
     e->last_occV = a.occV;
-    e->last_nV = (int64_t)e->x_B * items_per_pair(e->cfg);
+    e->last_nV = (int64_t)e->xb.B * items_per_pair(e->cfg);
     e->x_stage = 3;
     return CF_OK;
 }
@@ -2740,9 +2652,9 @@ int cf_xchg_grad_part(cf_engine* e, int32_t part) {
     CF_TRY(check_xchg(e, 2));
     if (part != 1 && part != 2) return fail(CF_EINVAL, "part must be 0, 1 or 2");
     if (part != e->x_part + 1) return fail(CF_ESTATE, "gradient parts run in order: 1 (local members), then 2");
-    StepArgs a = e->x_args;
+    StepArgs a = e->xb.args;
     a.member_pass = part;
-    if (part == 2) a.loss_partial = e->loss_partial + grad_blocks(e->x_args);
+    if (part == 2) a.loss_partial = e->loss_partial + grad_blocks(e->xb.args);
     {
         ProfScope ps(e, part == 1 ? CF_K_STEP : CF_K_STEP_REMOTE);
         CF_HIP(launch_grad(a, e->stream));
@@ -2750,21 +2662,21 @@ int cf_xchg_grad_part(cf_engine* e, int32_t part) {
     e->x_part = part;
     if (part == 2) {
         e->last_occV = a.occV;
-        e->last_nV = (int64_t)e->x_B * items_per_pair(e->cfg);
+        e->last_nV = (int64_t)e->xb.B * items_per_pair(e->cfg);
         e->x_stage = 3;
     }
     return CF_OK;
 }
 
 // loss partials of this exchange step's gradient launch(es)
-static int xchg_partials(cf_engine* e) { return grad_blocks(e->x_args) * (e->x_part == 2 ? 2 : 1); }
+static int xchg_partials(cf_engine* e) { return grad_blocks(e->xb.args) * (e->x_part == 2 ? 2 : 1); }
 
 // split step: the item rows' summed gradient into the bound buffer (the item
 // exchange can start), before the served gradients arrive for the users
 int cf_xchg_finish_items(cf_engine* e) {
     CF_TRY(check_xchg(e, 3));
     if (e->x_items_done) return fail(CF_ESTATE, "the items of this exchange step are already finished");
-    ApplyArgs p = apply_args(e, e->x_args, e->x_B, e->x_set, nullptr);   // the users' apply folds the loss
+    ApplyArgs p = apply_args(e, e->xb.args, e->xb.B, e->xb.set, nullptr);   // the users' apply folds the loss
     p.count_users = 0;
     p.n_partial = xchg_partials(e);
     if (p.count_items) {
@@ -2780,7 +2692,7 @@ int cf_xchg_finish(cf_engine* e, int64_t n_recv) {
     if (n_recv < 0 || n_recv > e->x_recv_cap) return fail(CF_EINVAL, "n_recv exceeds the bound receive capacity");
     CF_HIP(launch_xchg_accumulate(e->x_recv_ids, n_recv, e->shard_u0, e->x_serve_grads, e->GU,
                                   e->cfg.n_factors, e->stream));
-    ApplyArgs p = apply_args(e, e->x_args, e->x_B, e->x_set, e->loss);
+    ApplyArgs p = apply_args(e, e->xb.args, e->xb.B, e->xb.set, e->loss);
     p.served_ids = e->x_recv_ids;   // served rows with no local occurrence apply here
     p.served_own = e->x_own;
     p.nS = n_recv;
@@ -2832,11 +2744,7 @@ int cf_score_topk_ex(cf_engine* e, const int32_t* users, int32_t n, int32_t k, i
         std::vector<uint64_t> bits((size_t)nw, 0ull);
         for (int64_t j = 0; j < c.n_items; ++j)
             if (item_mask[j]) bits[(size_t)(j >> 6)] |= 1ull << (j & 63);
-        if (e->mask_words < nw) {
-            dfree(e->item_mask);
-            CF_TRY(dalloc(&e->item_mask, (size_t)nw));
-            e->mask_words = nw;
-        }
+        CF_TRY(e->item_mask.reserve((size_t)nw, "item mask"));
         CF_HIP(hipMemcpyAsync(e->item_mask, bits.data(), (size_t)nw * 8, hipMemcpyHostToDevice, e->stream));
         CF_HIP(hipStreamSynchronize(e->stream));   // `bits` is pageable and local
         d_mask = e->item_mask;
@@ -2858,20 +2766,12 @@ int cf_score_topk_ex(cf_engine* e, const int32_t* users, int32_t n, int32_t k, i
     const size_t row_bytes = (size_t)c.n_items * 4;
     const size_t budget = (size_t)512 << 20;
     int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, budget / row_bytes));
-    if ((size_t)chunk * row_bytes > e->keys_cap) {
-        dfree(e->keys);
-        CF_TRY(dalloc(&e->keys, (size_t)chunk * c.n_items));
-        e->keys_cap = (size_t)chunk * row_bytes;
-    }
-    int32_t* d_users = nullptr;
-    int32_t* d_idx = nullptr;
-    float* d_val = nullptr;
-    int r = CF_OK;
-    if ((r = dalloc(&d_users, (size_t)n)) || (r = dalloc(&d_idx, (size_t)n * k)) ||
-        (r = dalloc(&d_val, (size_t)n * k))) {
-        dfree(d_users); dfree(d_idx); dfree(d_val);
-        return r;
-    }
+    CF_TRY(e->keys.reserve((size_t)chunk * c.n_items, "score keys"));
+    DevBuf<int32_t> d_users, d_idx;
+    DevBuf<float> d_val;
+    CF_TRY(d_users.reset((size_t)n, "top-k users"));
+    CF_TRY(d_idx.reset((size_t)n * k, "top-k indices"));
+    CF_TRY(d_val.reset((size_t)n * k, "top-k values"));
     hipError_t he = hipMemcpyAsync(d_users, users, (size_t)n * 4, hipMemcpyHostToDevice, e->stream);
     for (int u0 = 0; he == hipSuccess && u0 < n; u0 += chunk) {
         const int m = std::min(chunk, n - u0);
@@ -2909,7 +2809,6 @@ int cf_score_topk_ex(cf_engine* e, const int32_t* users, int32_t n, int32_t k, i
     if (he == hipSuccess) he = hipMemcpy(idx_out, d_idx, (size_t)n * k * 4, hipMemcpyDefault);
     if (he == hipSuccess && val_out)
         he = hipMemcpy(val_out, d_val, (size_t)n * k * 4, hipMemcpyDefault);
-    dfree(d_users); dfree(d_idx); dfree(d_val);
     if (he != hipSuccess) return fail(CF_EHIP, std::string("cf_score_topk: ") + hipGetErrorString(he));
     return CF_OK;
 }
@@ -3164,6 +3063,12 @@ int cf_profile_reset(cf_engine* e) {
         }
         v.clear();
     }
+    return CF_OK;
+}
+
+int cf_debug_live_bytes(int64_t* device_bytes, int64_t* pinned_bytes) {
+    if (device_bytes) *device_bytes = g_live_bytes[0].load();
+    if (pinned_bytes) *pinned_bytes = g_live_bytes[1].load();
     return CF_OK;
 }
 

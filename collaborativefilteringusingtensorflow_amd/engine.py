@@ -531,6 +531,14 @@ class Engine(object):
         N.check(self._L.cf_profile_reset(self._h), "cf_profile_reset")
 
 
+def live_bytes():
+    """(device_bytes, pinned_bytes) the engines of this process hold right now
+    (cf_debug_live_bytes); equal before Engine(...) and after close() = no leak."""
+    dev, pin = ctypes.c_int64(0), ctypes.c_int64(0)
+    N.check(N.lib().cf_debug_live_bytes(ctypes.byref(dev), ctypes.byref(pin)), "cf_debug_live_bytes")
+    return int(dev.value), int(pin.value)
+
+
 def synth_degrees(n_users, mean_degree, seed):
     """Global indptr (int64, n_users+1) of the synthetic graph's degrees."""
     L = N.lib()

@@ -204,7 +204,7 @@ def test_two_rank_item_reduce_in_pieces(fold1, streams, pieces):
     assert np.array_equal(res[0][4], res[1][4])
 
 
-def _draw_ahead_worker(port, fold, q, exchange="allreduce", W=2, opts=None):
+def _draw_ahead_worker(port, fold, q, exchange="allreduce", W=2, opts=None, B=120):
     sys.path.insert(0, ROOT)
     import torch
     import torch.distributed as dist
@@ -222,13 +222,13 @@ def _draw_ahead_worker(port, fold, q, exchange="allreduce", W=2, opts=None):
         step, _ = make_gpu_sharded(e, 1682, 16, False, torch.device("cuda", 0), exchange=exchange)
         step.draw_ahead = ahead
         for _ in range(9):
-            step(batch_size=120)
+            step(batch_size=B)
         torch.cuda.synchronize()
         state = e.sampler_state()
-        nxt = e.sample(120)           # drops a drawn-ahead batch, rewinds the sampler
+        nxt = e.sample(B)             # drops a drawn-ahead batch, rewinds the sampler
         loss = e.take_loss()
         for _ in range(2):            # steps after the drop see clean counts
-            step(batch_size=120)
+            step(batch_size=B)
         torch.cuda.synchronize()
         out.append((e.get_table("user"), e.get_table("item"), e.get_table("acc_user"), state,
                     nxt[0], nxt[1], loss))
