@@ -129,7 +129,6 @@ struct cf_engine {
     DevBuf<int> hot_n;                 // rows handed out this batch
     DevBuf<unsigned long long> GV64;
     int fx_cap = 0;                    // batch size slotP64 / GU64 hold (0: re-size them)
-    int pair_prefetch = 0;   // measured slower at cfg2 (gradient launch +20 us, draw -2 us): off
     DevBuf<unsigned long long> pos_set;  // Pos(u) membership set of (u << 32 | i) keys
     uint64_t pos_mask = 0;
     int neg_check = 0;       // cf_set_option("neg_check"): 1 = Pos(u) set, 0 = CSR row scan
@@ -238,7 +237,6 @@ struct cf_engine {
         DevBuf<int32_t> cntP;            // pos_sort: positives per item
         DevBuf<int2> spec_ph;            // speculative negative counts (StepArgs::spec_ph)
         DevBuf<int> spec_n;
-        DevBuf<int4> pf_recs;            // prefetched pair records (StepArgs::pf_out)
         hipEvent_t prep_done = nullptr, apply_done = nullptr;
     } bs[2];
     int set = 0;
@@ -405,8 +403,7 @@ bool psort_active(const cf_engine* e, int B) {
     // deterministic mode keeps pos_sort (fixed-point sums, StepArgs::det_fx,
     // DESIGN 3.9) except on the multi-rank item reduce
     if (!psort_possible(e) || (e->pos_sort == 2 && B < kPsortAutoB) || (e->det && c.dense_item_apply) ||
-        e->hot_rep > 1 ||
-        e->neg_check == 2 || e->pipeline == 2)
+        e->hot_rep > 1 || e->pipeline == 2)
         return false;
     if (e->grad_path == 1 || (e->grad_path == 0 && c.model == CF_CML && c.n_neg == 5)) return false;
     return true;
@@ -671,7 +668,6 @@ StepArgs base_step_args(cf_engine* e, int B, int k) {
     a.indices_t = e->indices_t;
     a.pos_set = e->neg_check ? e->pos_set.p : nullptr;
     a.pos_mask = e->pos_mask;
-    a.lane_draw = e->neg_check == 2 ? 1 : 0;
     a.U = e->U; a.AU = e->AU; a.GU = e->GU;
     a.V = e->V; a.AV = e->AV; a.GV = e->GV;
     a.b = e->b; a.Ab = e->Ab; a.Gb = e->Gb;
@@ -1326,16 +1322,6 @@ int run_steps_device(cf_engine* e, int B, int n, double* loss_acc) {
     if (e->prep_side) CF_HIP(hipStreamWaitEvent(e->stream, e->bs[k].apply_done, 0));
     StepArgs a;
     CF_TRY(begin_step(e, B, nullptr, nullptr, nullptr, k, e->stream, &a));
-    // the positive-sorted gradient launch of step s fetches step s+1's pair
-    // records (StepArgs::pf_out); the draw of s+1 then reads them coalesced
-    // (sorted batches read their records coalesced already: no prefetch)
-    const bool pf = e->pair_prefetch && a.srec != nullptr && e->pipeline == 1 && !e->prep_side &&
-                    a.pos_set == nullptr && a.order == nullptr &&
-                    a.order_recs == nullptr;
-    if (pf && e->bs[1].pf_recs.cap < (size_t)B) {   // set 1's comes last: both hold B
-        CF_HIP(hipStreamSynchronize(e->stream));
-        for (auto& s : e->bs) CF_TRY(s.pf_recs.reset((size_t)B, "pf_recs"));
-    }
     for (int s = 0; s < n; ++s) {
         StepArgs nx{};
         const bool more = s + 1 < n;
@@ -1343,13 +1329,6 @@ int run_steps_device(cf_engine* e, int B, int n, double* loss_acc) {
             nx = base_step_args(e, B, k ^ 1);
             CF_TRY(check_det_args(e, nx));
             CF_TRY(sampler_args(e, B, &nx));
-            if (pf) {
-                a.pf_out = e->bs[k ^ 1].pf_recs;
-                a.pf_slot_base = nx.slot_base;
-                a.pf_perm = nx.perm;
-                a.pf_B = B;
-                nx.pre_pairs = e->bs[k ^ 1].pf_recs;
-            }
         }
         CF_TRY(finish_step(e, a, B, k, loss_acc, more ? &nx : nullptr));
         a = nx;
@@ -1805,7 +1784,7 @@ int cf_set_interactions(cf_engine* e, const int64_t* indptr, const int32_t* indi
     e->indptr.release(); e->indices.release(); e->pairs.release();
     e->indptr_t.release(); e->indices_t.release(); e->pos_set.release();
     CF_TRY(e->indptr.reset((size_t)c.n_users + 1, "indptr"));
-    CF_TRY(e->indices.reset((size_t)nnz + 4, "indices"));   // + 4: the draw's 16-B row loads never leave it
+    CF_TRY(e->indices.reset((size_t)nnz + 4, "indices"));   // + 4 ids of -1 padding (never empty)
     CF_HIP(hipMemsetAsync(e->indices + nnz, 0xFF, 16, e->stream));
     CF_TRY(e->pairs.reset((size_t)nnz, "pairs"));
     CF_HIP(hipMemcpyAsync(e->indptr, indptr, ((size_t)c.n_users + 1) * 8, hipMemcpyHostToDevice, e->stream));
@@ -2873,10 +2852,9 @@ int cf_set_option(cf_engine* e, const char* name, int64_t value) {
         return CF_OK;
     }
     if (n == "pair_prefetch") {
-        if (value < 0 || value > 1) return fail(CF_EINVAL, "pair_prefetch must be 0 or 1");
-        if (value == 1 && !pair_prefetch_built())
-            return fail(CF_EINVAL, "pair_prefetch: this build has the prefetch compiled out (-DCF_PAIR_PREFETCH=1)");
-        e->pair_prefetch = (int)value;
+        // the pair-record prefetch measured slower and was removed;
+        // the name is still accepted at 0 for callers that pass it
+        if (value != 0) return fail(CF_EINVAL, "pair_prefetch must be 0 (the prefetch was removed)");
         return CF_OK;
     }
     if (n == "prep_stream") {
@@ -2925,12 +2903,7 @@ int cf_set_option(cf_engine* e, const char* name, int64_t value) {
         return CF_OK;
     }
     if (n == "neg_check") {
-#ifdef CF_LANE_DRAW
-        if (value < 0 || value > 2) return fail(CF_EINVAL, "neg_check must be 0, 1 or 2");
-#else
-        if (value < 0 || value > 1)
-            return fail(CF_EINVAL, "neg_check must be 0 or 1 (2, the one-lane-per-pair draw, needs a -DCF_LANE_DRAW build)");
-#endif
+        if (value < 0 || value > 1) return fail(CF_EINVAL, "neg_check must be 0 or 1");
         CF_TRY(discard_pending(e));
         e->neg_check = (int)value;
         if (value >= 1 && e->pairs && !e->pos_set) CF_TRY(build_pos_set(e));

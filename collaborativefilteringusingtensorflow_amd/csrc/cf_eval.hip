@@ -250,17 +250,6 @@ __device__ __forceinline__ unsigned long long shfl_u64(unsigned long long v, int
     return ((unsigned long long)(uint32_t)hi << 32) | (uint32_t)lo;
 }
 
-#ifndef CF_FUSED_DPP_SORT
-// 1 (round 6): the compaction's bitonic exchanges read lane ^ s through DPP
-// (s <= 8, inside a 16-lane row) and gfx950's permlane16 / permlane32 swaps
-// (s = 16, 32) instead of ds_bpermute round trips through the LDS crossbar,
-// and a list of <= 64 entries is sorted in one register per lane.  Phase
-// stamps of the cfg5 pass (CF_FUSED_STAMPS, profiles/r06/r06s) put the
-// compactions and the waits they cause the block's other waves at ~18 % of
-// the wave cycles; measured cfg5 86.0 -> 89.8 TFLOP/s (same box,
-// tools/score_ab.py); 0: the shuffle form
-#define CF_FUSED_DPP_SORT 1
-#endif
 
 // the value lane ^ s holds (s < 64, a constant after unrolling), all lanes
 // active: DPP quad_perm for s = 1, 2; row_shr / row_shl with bank masks for
@@ -303,7 +292,6 @@ __device__ int wave_compact(unsigned long long* __restrict__ buf, int* cnt,
                             unsigned long long* thr, int keep, int k) {
     const int lane = lane_id();
     const int n = *cnt;
-#if CF_FUSED_DPP_SORT
     if (R >= 2 && n <= 64 && keep <= 64) {   // wave-uniform: one register per lane
         unsigned long long x = lane < n ? buf[lane] : 0ull;
 #pragma unroll
@@ -361,7 +349,6 @@ __device__ int wave_compact(unsigned long long* __restrict__ buf, int* cnt,
         }
         return m;
     }
-#endif
     if constexpr (R == 2) {   // the two-block-per-CU kernel's form (its register budget is tight)
         unsigned long long x0 = lane < n ? buf[lane] : 0ull;
         unsigned long long x1 = lane + 64 < n ? buf[lane + 64] : 0ull;
@@ -453,57 +440,6 @@ __device__ __forceinline__ int vs_off(int r, int kk) {
     return r * kFusedMaxD + ((((kk >> 2) ^ (r & 31)) << 2) | (kk & 3));
 }
 
-#ifndef CF_FUSED_PREFILTER
-// 1: the 16 prefilter compares first, the LDS reads only where a lane of the
-// wave passed -- measured even (cfg5 83.5 vs 84.8, cfg3 77.8 vs 75.9 TFLOP/s,
-// r04k; it spills 16-80 B at the 256-VGPR limit), so 0: the cost of the
-// candidate phase (84.7 -> 112.5 without it, CF_FUSED_EXP_NOCAND) is not the
-// mask reads
-#define CF_FUSED_PREFILTER 0
-#endif
-#ifndef CF_FUSED_FCMP
-// 1 (round 4): the register prefilter compares the float score against the
-// float form of its row's threshold word -- one v_cmp per score, no key
-// conversion, no per-row (R < nu) mask -- and the wave takes the exact path
-// only when some lane passed some score (rare once the thresholds have
-// risen); 0: the key-word prefilter per score, each with its own branch
-#define CF_FUSED_FCMP 1
-#endif
-#ifndef CF_FUSED_BPREFETCH
-#define CF_FUSED_BPREFETCH 0   // 1: read each MFMA group's B operand one group ahead (measured slower: 74 vs 84.5 TF)
-#endif
-#ifndef CF_FUSED_STRICT
-// 1 (round 6): the exact candidate test reads thr[R] only for a score equal
-// to its row's threshold float; 0: every prefilter pass reads it.  Measured
-// even (89.7 vs 89.8 TFLOP/s): the exact path's cost is not that read.  (Slots
-// from one LDS atomic per row and half-wave, ballot ranks and readlanes,
-// measured slower: cfg5 86.8 vs 89.5 TFLOP/s, profiles/r06/r06s/r06s7)
-#define CF_FUSED_STRICT 1
-#endif
-#ifndef CF_FUSED_MASK_AHEAD
-// 1 (round 6): the users' threads build the next tile's train masks during
-// this tile's candidate phase (two mask buffers, +512 B of LDS), so the
-// cursor walk no longer holds the other waves at the staging barrier, and
-// with the prefetched tile that barrier goes (two per step instead of
-// three): cfg5 89.7 -> 91.2 TFLOP/s; 0: the masks are built in the staging
-// phase of their own tile
-#define CF_FUSED_MASK_AHEAD 1
-#endif
-#ifndef CF_FUSED_CURSOR2
-// 1 (round 6): the train-row cursor keeps the next TWO items in registers, so
-// consuming one issues the load of the one after without waiting for it;
-// 0: each consumption waits for its dependent load (wave 0 of the block, at
-// nearly every step of a 64-user block).  Measured even (86.1 vs 85.9,
-// 90.7 vs 91.2 TFLOP/s with the masks built ahead), so 0
-#define CF_FUSED_CURSOR2 0
-#endif
-#ifndef CF_FUSED_SETPRIO
-// 1 (round 5 experiment): a wave raises its issue priority for its MFMA
-// stream (s_setprio 3) and drops it for the candidate phase, so the SIMD's
-// other wave -- of the other block -- fills the gaps instead of both waves'
-// MFMA streams and candidate phases lining up
-#define CF_FUSED_SETPRIO 0
-#endif
 // CAP: candidate slots per user.  kFusedCap (92, k <= 28): ~80 KB of LDS,
 // two blocks per CU.  kFusedCapWide (192, k <= 128; round 5, GBPR's topN =
 // 100): ~130 KB, one block per CU.
@@ -523,7 +459,7 @@ void fused_topk_kernel(FusedTopkArgs a) {
     // users' threads during this tile's candidate phase).  BPR only: GBPR's
     // bias tile and CML's norms leave no room for the second buffer beside
     // two blocks per CU (81,928 B > 80 KiB)
-    constexpr bool AHEAD = CF_FUSED_MASK_AHEAD && MODEL == BPR;
+    constexpr bool AHEAD = MODEL == BPR;
     __shared__ unsigned long long mask_buf[AHEAD ? 2 : 1][NU];
     __shared__ int cnt[NU];
     __shared__ float unorm[NU];
@@ -541,11 +477,7 @@ void fused_topk_kernel(FusedTopkArgs a) {
     // the score words of the thresholds of this lane's 16 output rows, kept in
     // registers: a score whose key word is below its row's cannot enter the
     // list, so most scores are rejected without touching LDS
-#if CF_FUSED_FCMP
     float thf[16];   // key_float of the threshold word; +inf for rows past nu
-#else
-    uint32_t thi[16];
-#endif
     int thi_ver = -1;
     const int nu = (a.n_users - u0) < NU ? (a.n_users - u0) : NU;
 
@@ -574,9 +506,6 @@ void fused_topk_kernel(FusedTopkArgs a) {
     }
     int64_t cur = 0, end = 0;                // train-row cursor of user `tid` (tid < 64)
     int64_t nxt = INT64_MAX;                 // the train item at the cursor, kept in a register
-#if CF_FUSED_CURSOR2
-    int nxt2 = INT_MAX;                      // the one after it, loaded a consumption ahead
-#endif
     if (tid < NU) {
         thr[tid] = 0ull;
         cnt[tid] = 0;
@@ -585,9 +514,6 @@ void fused_topk_kernel(FusedTopkArgs a) {
             cur = a.indptr[u];
             end = a.indptr[u + 1];
             if (cur < end) nxt = a.indices[cur];
-#if CF_FUSED_CURSOR2
-            if (cur + 1 < end) nxt2 = a.indices[cur + 1];
-#endif
         }
     }
     // the next item tile is loaded into registers during this tile's MFMA and
@@ -626,14 +552,7 @@ void fused_topk_kernel(FusedTopkArgs a) {
         while (nxt < jt + kFusedItems) {   // sorted row: no load unless an item is consumed
             m |= 1ull << (int)(nxt - jt);
             ++cur;
-#if CF_FUSED_CURSOR2
-            // the next item is already in a register; the load issued
-            // here is waited on only at a later consumption
-            nxt = nxt2 == INT_MAX ? INT64_MAX : (int64_t)nxt2;
-            nxt2 = cur + 1 < end ? a.indices[cur + 1] : INT_MAX;
-#else
             nxt = cur < end ? (int64_t)a.indices[cur] : INT64_MAX;
-#endif
         }
         mask_buf[slot][tid] = m;
     };
@@ -673,36 +592,15 @@ void fused_topk_kernel(FusedTopkArgs a) {
         // so that barrier is this step's
         if (!AHEAD || !vec) __syncthreads();
         CF_STAMP(1);
-#ifdef CF_FUSED_EXP_NOLOAD   // attribution: no tile streaming (stale tile)
-        const bool more = false;
-#else
         const bool more = vec && j0 + kFusedItems < a.n_items;
-#endif
         if (more) load_tile(j0 + kFusedItems);
         // ---- 32 x 32 tile per wave on the matrix cores --------------------------
-        if (CF_FUSED_SETPRIO) __builtin_amdgcn_s_setprio(3);
         floatx16 acc;
 #pragma unroll
         for (int q = 0; q < 16; ++q) acc[q] = 0.f;
         float vsq = 0.f;
         const int br = wc * 32 + c;              // B operand row (item) of this lane
-#ifndef CF_FUSED_EXP_NOMFMA   // attribution builds (wrong results by design)
-#if CF_FUSED_BPREFETCH
-        auto bop = [&](int t0) {   // address formed at use (hoisted: 16 VGPRs)
-            int r = br, hd = h * Dh;
-            asm volatile("" : "+v"(r), "+v"(hd));
-            return *reinterpret_cast<const float4*>(Vs + vs_off(r, hd + t0));
-        };
-#else
         auto bop = [&](int t0) { return *reinterpret_cast<const float4*>(Vs + vs_off(br, h * Dh + t0)); };
-#endif
-        auto mfma4b = [&](int t0, const float4 b4) {
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ua[t0 + 0], b4.x, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ua[t0 + 1], b4.y, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ua[t0 + 2], b4.z, acc, 0, 0, 0);
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ua[t0 + 3], b4.w, acc, 0, 0, 0);
-            if (MODEL == CML) vsq += b4.x * b4.x + b4.y * b4.y + b4.z * b4.z + b4.w * b4.w;
-        };
         auto mfma4 = [&](int t0) {
             const float4 b4 = bop(t0);
             acc = __builtin_amdgcn_mfma_f32_32x32x2f32(ua[t0 + 0], b4.x, acc, 0, 0, 0);
@@ -715,27 +613,13 @@ void fused_topk_kernel(FusedTopkArgs a) {
             // branch-free: a conditional per k-chunk made the compiler wait
             // for every outstanding global load (the prefetched next tile)
             // at each chunk (s_waitcnt vmcnt(0) before the LDS reads)
-#if CF_FUSED_BPREFETCH
-            // the next group's B operand is read before this group's MFMAs,
-            // so no MFMA group waits on its own LDS read
-            float4 bc = bop(0);
-#pragma unroll
-            for (int t0 = 0; t0 < kAH; t0 += 4) {
-                const float4 bn4 = bop(t0 + 4 < kAH ? t0 + 4 : t0);
-                mfma4b(t0, bc);
-                bc = bn4;
-            }
-#else
 #pragma unroll
             for (int t0 = 0; t0 < kAH; t0 += 4) mfma4(t0);
-#endif
         } else {
 #pragma unroll
             for (int t0 = 0; t0 < kAH; t0 += 4)
                 if (t0 < Dh) mfma4(t0);   // block-uniform
         }
-#endif
-        if (CF_FUSED_SETPRIO) __builtin_amdgcn_s_setprio(0);
         CF_STAMP(2);
         float vnorm = 0.f;
         if (MODEL == CML) vnorm = vsq + __shfl_xor(vsq, 32, 64);   // |v_col|^2
@@ -743,8 +627,6 @@ void fused_topk_kernel(FusedTopkArgs a) {
         const int jl = wc * 32 + c;
         const int64_t J = j0 + jl;
         const unsigned long long* __restrict__ mask = mask_buf[mslot];
-#ifndef CF_FUSED_EXP_NOCAND
-#if CF_FUSED_FCMP
         if (thi_ver != thr_ver) {   // block-uniform (thr_ver changes only between barriers)
             thi_ver = thr_ver;
 #pragma unroll
@@ -771,7 +653,6 @@ void fused_topk_kernel(FusedTopkArgs a) {
         CF_STAMP(11);
         if (__ballot(anyp) != 0ull) {   // wave-uniform
             CF_STAMP_COUNT(9);
-#if CF_FUSED_STRICT
             // a score strictly above its row's threshold float has a key above
             // the threshold key (float_key is order-preserving; thf is the
             // float of thr[R]'s high word, refreshed with it): only an equal
@@ -792,96 +673,8 @@ void fused_topk_kernel(FusedTopkArgs a) {
                     }
                 }
             }
-#else
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int R = wr * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
-                float s = acc[q];
-                if (MODEL == GBPR) s += bj_;
-                if (MODEL == CML) s = 2.f * s - vnorm - unorm[R];
-                if (!(s < thf[q]) && R < nu && J < a.n_items && !((mask[R] >> jl) & 1ull)) {
-                    const unsigned long long key = ((unsigned long long)float_key(s) << 32) |
-                                                   (0xFFFFFFFFull - (unsigned long long)J);
-                    if (key > thr[R]) {
-                        const int pos = atomicAdd(&cnt[R], 1);
-                        buf[R * CAP + pos] = key;
-                    }
-                }
-            }
-#endif
         }
         CF_STAMP(12);
-#else
-        if (thi_ver != thr_ver) {   // block-uniform (thr_ver changes only between barriers)
-            thi_ver = thr_ver;
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                const int R = wr * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
-                thi[q] = R < nu ? (uint32_t)(thr[R] >> 32) : 0xFFFFFFFFu;
-            }
-        }
-#endif
-#if CF_FUSED_FCMP
-        // (above)
-#elif CF_FUSED_PREFILTER
-        // round 4: the register prefilter for all 16 scores first -- no LDS
-        // read -- and the train mask, the exact threshold and the insertion
-        // only where some lane of the wave passed (rare once the thresholds
-        // have risen).  Attribution: the candidate phase cost the pass 84.7 ->
-        // 112.5 TFLOP/s (CF_FUSED_EXP_NOCAND), its 16 mask reads per lane
-        // per tile were issued whatever the prefilter said.
-        const float bj_ = (MODEL == GBPR) ? bt[jl] : 0.f;
-        uint32_t pass = 0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int R = wr * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
-            float s = acc[q];
-            if (MODEL == GBPR) s += bj_;
-            if (MODEL == CML) s = 2.f * s - vnorm - unorm[R];   // -|u - v|^2
-            // key > thr[R] implies fk >= thi[q]: a pure prefilter
-            pass |= (float_key(s) >= thi[q]) ? (1u << q) : 0u;
-        }
-        if (__ballot(pass != 0u) != 0ull) {   // wave-uniform
-#pragma unroll
-            for (int q = 0; q < 16; ++q) {
-                if (!((pass >> q) & 1u)) continue;
-                const int R = wr * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
-                float s = acc[q];
-                if (MODEL == GBPR) s += bj_;
-                if (MODEL == CML) s = 2.f * s - vnorm - unorm[R];
-                const uint32_t fk = float_key(s);
-                if (R < nu && J < a.n_items && !((mask[R] >> jl) & 1ull)) {
-                    const unsigned long long key = ((unsigned long long)fk << 32) |
-                                                   (0xFFFFFFFFull - (unsigned long long)J);
-                    if (key > thr[R]) {
-                        const int pos = atomicAdd(&cnt[R], 1);
-                        buf[R * CAP + pos] = key;
-                    }
-                }
-            }
-        }
-#else
-#pragma unroll
-        for (int q = 0; q < 16; ++q) {
-            const int R = wr * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
-            float s = acc[q];
-            if (MODEL == GBPR) s += bt[jl];
-            if (MODEL == CML) s = 2.f * s - vnorm - unorm[R];   // -|u - v|^2
-            const uint32_t fk = float_key(s);
-            // key > thr[R] implies fk >= thi[q]: a pure prefilter
-            if (fk >= thi[q] && R < nu && J < a.n_items && !((mask[R] >> jl) & 1ull)) {
-                const unsigned long long key = ((unsigned long long)fk << 32) |
-                                               (0xFFFFFFFFull - (unsigned long long)J);
-                if (key > thr[R]) {
-                    const int pos = atomicAdd(&cnt[R], 1);
-                    buf[R * CAP + pos] = key;
-                }
-            }
-        }
-#endif
-#else
-        if (acc[0] == 12345.f && J == 7) cnt[0] = 1;   // keep the MFMA result live
-#endif
         if (AHEAD && tid < NU && j0 + kFusedItems < a.n_items)
             build_mask(j0 + kFusedItems, mslot ^ 1);   // read after this tile's barriers
         if (AHEAD) mslot ^= 1;
@@ -1155,22 +948,11 @@ __global__ __launch_bounds__(kBlock, 2) void fused_topk_pipe_kernel(FusedTopkArg
         };
         if (Dh == kAH) {
             // one previous-tile row test per group of four MFMAs (16 and 16)
-#if CF_FUSED_BPREFETCH
-            float4 bc = bop(0);   // the next group's B operand read ahead
-#pragma unroll
-            for (int t0 = 0; t0 < kAH; t0 += 4) {
-                const float4 bn4 = bop(t0 + 4 < kAH ? t0 + 4 : t0);
-                mfma4(t0, bc);
-                pass |= pass_of(t0 >> 2);
-                bc = bn4;
-            }
-#else
 #pragma unroll
             for (int t0 = 0; t0 < kAH; t0 += 4) {
                 mfma4(t0, bop(t0));
                 pass |= pass_of(t0 >> 2);
             }
-#endif
         } else {
 #pragma unroll
             for (int t0 = 0; t0 < kAH; t0 += 4)
@@ -1407,15 +1189,9 @@ __global__ __launch_bounds__(kWsThreads, 1) void fused_topk_ws_kernel(FusedTopkA
                 }
             }
         } else {
-#ifndef CF_WS_EXP_NOSTAGE   // attribution only (stale tiles, wrong results)
             if (t + 1 < ntile) stage_tile(t + 1);
             if (vec && t + 2 < ntile) load_tile((t + 2) * kFusedItems);
-#endif
-#ifdef CF_WS_EXP_NOCAND   // attribution only (no candidates)
-            if (false) {
-#else
             if (t >= 1 && Rc < nu) {
-#endif
                 // tile t-1's scores of this lane's row, columns ch*16 .. +16
                 const int64_t jb = (t - 1) * kFusedItems + ch * 16;
                 const float* S_ = Sc[(t - 1) & 1] + Rc * kWsSP + ch * 16;

@@ -77,17 +77,6 @@ struct StepArgs {
     // (u << 32 | i) keys, linear probing (null: scan the user's CSR row)
     const unsigned long long* __restrict__ pos_set;
     uint64_t pos_mask;                      // capacity - 1 (power of two)
-    // pair-record prefetch (round 3, cf_set_option "pair_prefetch"): the
-    // positive-sorted gradient launch of step s also fetches step s+1's
-    // shuffled pair records -- pairs[permute(pf_slot_base + p, pf_perm)] for
-    // p < pf_B, one per 16-lane group -- into pf_out[p], so that step s+1's
-    // draw (pre_pairs = that buffer) reads them coalesced and starts at the
-    // row scan.  Same records, same batches.  null = off
-    int4* __restrict__ pf_out;
-    uint64_t pf_slot_base;
-    PermKey pf_perm;
-    int pf_B;
-    const int4* __restrict__ pre_pairs;     // the draw's record of pair p at [p] (null: pairs[permute(..)])
     // sorted batches (round 5, cf_set_option "sorted_batches"): the epoch's
     // pair indices batch by batch, each batch in pair (CSR) order -- the draw
     // takes pairs[order[slot]] instead of pairs[permute(slot)]: the same
@@ -128,7 +117,6 @@ struct StepArgs {
     // set, and a discarded draw uncounts the phantoms.  null = off
     int2* __restrict__ spec_ph;             // [B * W]
     int* __restrict__ spec_n;
-    int lane_draw;                          // 1: one lane per pair (neg_check 2, with the set)
     // tables (updated in place for rows seen once in the batch)
     float* __restrict__ U; float* __restrict__ AU; float* __restrict__ GU;
     float* __restrict__ V; float* __restrict__ AV; float* __restrict__ GV;
@@ -502,8 +490,6 @@ hipError_t launch_epoch_count(const PermKey& p, int64_t nnz, int B, const int4* 
                               int32_t* out_idx, void* tmp, size_t tmp_bytes, hipStream_t s);
 // a discarded draw's phantoms (StepArgs::spec_ph): uncount them, re-zero spec_n
 hipError_t launch_uncount_spec(const int2* ph, int* n, int32_t* cnt, hipStream_t s);
-// grad_sort_kernel carries the pair-record prefetch (StepArgs::pf_out)
-bool pair_prefetch_built();
 hipError_t launch_build_pos_set(const int4* pairs, int64_t nnz, unsigned long long* set,
                                 uint64_t mask, hipStream_t s);
 hipError_t launch_build_pairs(const int64_t* indptr, const int32_t* indices, int64_t n_users,

@@ -182,13 +182,14 @@ int grad_blocks(const StepArgs& a, bool with_draw) {
         return (a.B + CF_SORT_TILES * kPsortPPB - 1) / (CF_SORT_TILES * kPsortPPB);
     const int fw = fast_w(a);
     const int B = a.B;
-    const int gpb = (CF_GRAD_WAVE_BLOCKS && !with_draw) ? kWave / kGL : kGroupsPerBlock;
     const int p5 = (a.model == GBPR && epl_for(a.d) <= 4) ? CF_FAST_PAIRS_GBPR_W5 : CF_FAST_PAIRS_W5;
-    const int ppb = fw == 1 ? CF_FAST_PAIRS_W1 * gpb
-                  : fw == 5 ? p5 * gpb : kPairsPerBlock;
+    const int ppb = fw == 1 ? CF_FAST_PAIRS_W1 * kGroupsPerBlock
+                  : fw == 5 ? p5 * kGroupsPerBlock : kPairsPerBlock;
     return (B + ppb - 1) / ppb;
 }
 
+// B / 4: the split exchange step (part 2) also keeps two passes' partials of
+// B / 16 blocks each side by side in loss_partial
 int grad_blocks_max(int B) { return (B + kWave / kGL - 1) / (kWave / kGL); }
 
 hipError_t launch_prep(const StepArgs& a, hipStream_t s) {
@@ -206,7 +207,6 @@ hipError_t launch_grad(const StepArgs& a, hipStream_t s, const StepArgs* next) {
     if (a.B <= 0) return next ? launch_prep(*next, s) : hipSuccess;
     if (next && next->model != a.model) return hipErrorInvalidValue;
     if (a.srec != nullptr && fast_w(a) == 0) return hipErrorInvalidValue;   // pos_sort: phased kernel only
-    if (a.pf_out != nullptr && a.srec == nullptr) return hipErrorInvalidValue;   // only grad_sort_kernel prefetches
     switch (a.model) {
         case BPR: return launch_grad_bpr(a, next, s);
         case GBPR: return launch_grad_gbpr(a, next, s);
@@ -226,10 +226,6 @@ static int apply_grid(const ApplyArgs& a) {
     if (blocks < 1) blocks = 1;        // block 0 still reduces the loss
     return (int)blocks;
 }
-
-#ifndef CF_APPLY_WAVE_BLOCKS
-#define CF_APPLY_WAVE_BLOCKS 0
-#endif
 
 template <bool HOT>
 static hipError_t launch_apply_h(const ApplyArgs& a, hipStream_t s) {
@@ -259,32 +255,19 @@ static hipError_t launch_apply_ps_t(const ApplyArgs& p, const StepArgs* nx, hipS
     const int nbI = (int)nbI64, nbW = (int)std::max<int64_t>(nbW64, nbI64 == 0 ? 1 : 0);   // block 0 folds the loss
     const dim3 grid(nbI + nbW + np), block(kBlock);
     const StepArgs n = nx ? *nx : StepArgs{};
-    const bool full = CF_ASSUME_FULL_APPLY && p.d == kGL * epl_for(p.d);
     if (np > 0) {
         switch (epl_for(p.d)) {
             case 1: hipLaunchKernelGGL((apply_ps_kernel<1, true, PS, FX>), grid, block, 0, s, p, n, nbI, nbW); break;
             case 2: hipLaunchKernelGGL((apply_ps_kernel<2, true, PS, FX>), grid, block, 0, s, p, n, nbI, nbW); break;
-            case 4:
-                if (full) hipLaunchKernelGGL((apply_ps_kernel<4, true, PS, FX, true>), grid, block, 0, s, p, n, nbI, nbW);
-                else hipLaunchKernelGGL((apply_ps_kernel<4, true, PS, FX>), grid, block, 0, s, p, n, nbI, nbW);
-                break;
-            default:
-                if (full) hipLaunchKernelGGL((apply_ps_kernel<8, true, PS, FX, true>), grid, block, 0, s, p, n, nbI, nbW);
-                else hipLaunchKernelGGL((apply_ps_kernel<8, true, PS, FX>), grid, block, 0, s, p, n, nbI, nbW);
-                break;
+            case 4: hipLaunchKernelGGL((apply_ps_kernel<4, true, PS, FX>), grid, block, 0, s, p, n, nbI, nbW); break;
+            default: hipLaunchKernelGGL((apply_ps_kernel<8, true, PS, FX>), grid, block, 0, s, p, n, nbI, nbW); break;
         }
     } else {
         switch (epl_for(p.d)) {
             case 1: hipLaunchKernelGGL((apply_ps_kernel<1, false, PS, FX>), grid, block, 0, s, p, n, nbI, nbW); break;
             case 2: hipLaunchKernelGGL((apply_ps_kernel<2, false, PS, FX>), grid, block, 0, s, p, n, nbI, nbW); break;
-            case 4:
-                if (full) hipLaunchKernelGGL((apply_ps_kernel<4, false, PS, FX, true>), grid, block, 0, s, p, n, nbI, nbW);
-                else hipLaunchKernelGGL((apply_ps_kernel<4, false, PS, FX>), grid, block, 0, s, p, n, nbI, nbW);
-                break;
-            default:
-                if (full) hipLaunchKernelGGL((apply_ps_kernel<8, false, PS, FX, true>), grid, block, 0, s, p, n, nbI, nbW);
-                else hipLaunchKernelGGL((apply_ps_kernel<8, false, PS, FX>), grid, block, 0, s, p, n, nbI, nbW);
-                break;
+            case 4: hipLaunchKernelGGL((apply_ps_kernel<4, false, PS, FX>), grid, block, 0, s, p, n, nbI, nbW); break;
+            default: hipLaunchKernelGGL((apply_ps_kernel<8, false, PS, FX>), grid, block, 0, s, p, n, nbI, nbW); break;
         }
     }
     return hipGetLastError();
@@ -307,20 +290,6 @@ static bool dense_rows_apply(const ApplyArgs& a) {
 }
 
 hipError_t launch_apply(const ApplyArgs& a, hipStream_t s) {
-    if (CF_APPLY_WAVE_BLOCKS) {
-        // one-wave apply blocks have no pos_sort owner rule: refuse rather
-        // than skip or double-apply an item whose positives count in cntP
-        if (a.cntP != nullptr || a.hotP != nullptr) return hipErrorInvalidValue;
-        const dim3 grid(apply_grid(a)), block(kWave);
-        switch (epl_for(a.d)) {
-            case 1: hipLaunchKernelGGL(apply_wave_kernel<1>, grid, block, 0, s, a); break;
-            case 2: hipLaunchKernelGGL(apply_wave_kernel<2>, grid, block, 0, s, a); break;
-            case 4: hipLaunchKernelGGL(apply_wave_kernel<4>, grid, block, 0, s, a); break;
-            case 8: hipLaunchKernelGGL(apply_wave_kernel<8>, grid, block, 0, s, a); break;
-            default: hipLaunchKernelGGL(apply_wave_kernel<16>, grid, block, 0, s, a); break;
-        }
-        return hipGetLastError();
-    }
     if (a.cntP != nullptr) {   // pos_sort (d <= 128, no served rows, no deterministic tiles)
         if (a.hotP != nullptr || a.nS > 0 || epl_for(a.d) > 8) return hipErrorInvalidValue;
         return launch_apply_ps(a, nullptr, s);
@@ -498,8 +467,6 @@ hipError_t launch_uncount_spec(const int2* ph, int* n, int32_t* cnt, hipStream_t
     hipLaunchKernelGGL(uncount_spec_kernel, dim3(1), dim3(kBlock), 0, s, ph, n, cnt);
     return hipGetLastError();
 }
-
-bool pair_prefetch_built() { return CF_PAIR_PREFETCH != 0; }
 
 hipError_t launch_uncount(const int32_t* occ, int64_t n, int32_t* cnt, hipStream_t s) {
     if (n <= 0) return hipSuccess;

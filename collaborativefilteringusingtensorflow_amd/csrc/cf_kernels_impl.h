@@ -45,40 +45,96 @@
 #include "cf_kernels.h"
 #include "cf_device.h"
 
+// ---------------------------------------------------------------------------
+// Tunables: plain numbers, overridable with -D (CF_EXTRA_FLAGS in build.py).
+// The defaults are the measured best; DESIGN 8 has the figures.
+// ---------------------------------------------------------------------------
+#ifndef CF_PREP_GL
+#define CF_PREP_GL 8                // lanes per pair in the draw at W > 1 (a power of two, 2..16)
+#endif
+#ifndef CF_PREP_CHUNKS
+#define CF_PREP_CHUNKS 8            // row chunks in flight per candidate test (CF_PREP_GL lanes)
+#endif
+#ifndef CF_PREP_GL_W1
+#define CF_PREP_GL_W1 4             // lanes per pair in the draw at W = 1
+#endif
+#ifndef CF_PREP_CHUNKS_W1
+#define CF_PREP_CHUNKS_W1 (64 / CF_PREP_GL_W1)   // row chunks in flight at W = 1: one scan covers 64 ids
+#endif
+#ifndef CF_SORT_MIN_WAVES
+#define CF_SORT_MIN_WAVES 1         // grad_sort_kernel: minimum waves per SIMD (1: the compiler's budget)
+#endif
+#ifndef CF_SORT_TILES
+#define CF_SORT_TILES 1             // positive-sorted tiles per block (grad_fast_body)
+#endif
+#ifndef CF_LDS_WAVES
+#define CF_LDS_WAVES 1              // grad_lds_kernel: minimum waves per SIMD (LDS alone allows 4)
+#endif
+#ifndef CF_LDS_WAVES_GBPR
+#define CF_LDS_WAVES_GBPR 1         // the same for GBPR (4: 128 VGPRs, 12-B spill, measured slower, r04j)
+#endif
+#ifndef CF_APPLY_NF
+#define CF_APPLY_NF 4               // slot rows in flight per group in the apply (8: occupancy 5, slower)
+#endif
+#ifndef CF_APPLY_NF_PS
+#define CF_APPLY_NF_PS 8            // rows in flight per group in the pos_sort item apply
+#endif
+#ifndef CF_APPLY_MIN_WAVES
+#define CF_APPLY_MIN_WAVES 1        // apply_ps_kernel: minimum waves per SIMD (7: 12-B spill, even to slower)
+#endif
+#ifndef CF_APPLY_DETECT_WAVES
+#define CF_APPLY_DETECT_WAVES 1     // waves of an apply block that find owners (4 measured slower)
+#endif
+#ifndef CF_APPLY_CHUNK
+#define CF_APPLY_CHUNK 64           // work items per detecting wave (<= 64; 32 and 16 delay the fused draw)
+#endif
+#ifndef CF_FAST_PAIRS_W1
+#define CF_FAST_PAIRS_W1 1          // pairs per group, phased kernel at W = 1 (cfg2: P=1 44.2 us .. P=4 61.9)
+#endif
+#ifndef CF_FAST_PAIRS_W5
+#define CF_FAST_PAIRS_W5 1          // pairs per group, phased kernel at W = 5
+#endif
+#ifndef CF_FAST_PAIRS_GBPR_W5
+#define CF_FAST_PAIRS_GBPR_W5 2     // the same for GBPR at d <= 64 (cfg4 grad 164.9 -> 157.6 us)
+#endif
+// CF_GRAD_WAVES_PER_EU (no default): minimum waves per SIMD of grad_fast_kernel
+#ifdef CF_GRAD_WAVES_PER_EU
+#define CF_GRAD_ATTR __attribute__((amdgpu_waves_per_eu(CF_GRAD_WAVES_PER_EU, 8)))
+#else
+#define CF_GRAD_ATTR
+#endif
+// Not a tunable number: 1 puts the fused draw's blocks after every apply block
+// (the order before round 4).  It stays a switch because the compiler cannot
+// prove that order's arm unreachable in apply_ps_kernel, so resolving it
+// changes the fused instantiations' code (see there).
+#ifndef CF_APPLY_DRAW_TAIL
+#define CF_APPLY_DRAW_TAIL 0
+#endif
+
 namespace cfk {
 
 // ---------------------------------------------------------------------------
 // 16-lane group helpers.  A row of d floats is held as EPL slots per lane.
-// Rows that fill every slot (d == 16*EPL: d = 16, 32, 64, 128, 256) use the
-// vector layout: lane gl holds VW = min(EPL, 4) contiguous floats of each
-// 64*VW-byte stripe, so one dwordx{VW} instruction moves a whole stripe of
-// four rows (one per group of the wave) -- a 256-B row (d = 64) is one
-// 16-B-per-lane access.  Other d use the scalar layout: element s*16 + gl,
+// Wide rows that fill every slot (EPL >= 8 and d == 16*EPL: d = 128, 256) use
+// the vector layout: lane gl holds 4 contiguous floats of each 256-byte
+// stripe, so one dwordx4 instruction moves a whole stripe of four rows (one
+// per group of the wave).  Other d use the scalar layout: element s*16 + gl,
 // masked by e < d.  Arithmetic is layout-blind (slot-wise, with group
 // reductions); memory stays row-major either way.
 // ---------------------------------------------------------------------------
-// The vector layout measured no faster on the gather (46.0 vs 44.9 us, cfg2
-// grad without atomics) and its float atomics touch four 64-B segments per
-// row-stripe instead of one (grad 105 vs 50 us), so the scalar layout is the
-// default; -DCF_VEC_ROWS=1 builds the vector layout for experiments.
-#ifndef CF_VEC_ROWS
-#define CF_VEC_ROWS 0
-#endif
-// Round 5: rows of d > 64 (EPL >= 8: cfg3 / cfg5's d = 128) take the vector
-// layout by default -- the apply's 512-B slot and table rows move as two
-// float4 per lane: cfg5 apply + draw 96.2 -> 88.8 us, 0.2013 -> 0.1940
-// ms/step; the d = 64 kernels keep the scalar one (cfg2 gradient 164.5 ->
-// 194.5 us with it, cfg4 apply 77.4 -> 86.0; profiles/r05/ab/r05h_*).  The
-// mapping is per kernel (memory rows are always natural order), so kernels
-// with different layouts exchange rows freely
-#ifndef CF_VEC_ROWS_WIDE
-#define CF_VEC_ROWS_WIDE 1
-#endif
+// With the vector layout at d > 64 (cfg3 / cfg5's d = 128)
+// the apply's 512-B slot and table rows move as two float4 per lane: cfg5
+// apply + draw 96.2 -> 88.8 us, 0.2013 -> 0.1940 ms/step; the d <= 64 kernels
+// keep the scalar one (cfg2 gradient 164.5 -> 194.5 us with the vector
+// layout, cfg4 apply 77.4 -> 86.0; profiles/r05/ab/r05h_*: its float atomics
+// touch four 64-B segments per row-stripe instead of one).  The mapping is
+// per kernel (memory rows are always natural order), so kernels with
+// different layouts exchange rows freely
 template <int EPL>
-__host__ __device__ constexpr bool vec_rows() { return CF_VEC_ROWS || (CF_VEC_ROWS_WIDE && EPL >= 8); }
+__host__ __device__ constexpr bool vec_rows() { return EPL >= 8; }
 template <int EPL>
 struct Lay {
-    static constexpr int VW = vec_rows<EPL>() ? (EPL >= 4 ? 4 : EPL) : 1;
+    static constexpr int VW = vec_rows<EPL>() ? 4 : 1;
     static constexpr int NQ = EPL / VW;  // stripes per row
 };
 
@@ -97,15 +153,8 @@ __device__ __forceinline__ void row_ld(const float* __restrict__ row, int d, int
 #pragma unroll
         for (int q = 0; q < Lay<EPL>::NQ; ++q) {
             const float* p = row + q * (kGL * VW) + gl * VW;
-            if constexpr (VW == 4) {
-                const float4 v = *reinterpret_cast<const float4*>(p);
-                x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w;
-            } else if constexpr (VW == 2) {
-                const float2 v = *reinterpret_cast<const float2*>(p);
-                x[2 * q] = v.x; x[2 * q + 1] = v.y;
-            } else {
-                x[q] = p[0];
-            }
+            const float4 v = *reinterpret_cast<const float4*>(p);
+            x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w;
         }
     } else {
 #pragma unroll
@@ -123,13 +172,7 @@ __device__ __forceinline__ void row_st(float* __restrict__ row, int d, int gl, c
 #pragma unroll
         for (int q = 0; q < Lay<EPL>::NQ; ++q) {
             float* p = row + q * (kGL * VW) + gl * VW;
-            if constexpr (VW == 4) {
-                *reinterpret_cast<float4*>(p) = make_float4(x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]);
-            } else if constexpr (VW == 2) {
-                *reinterpret_cast<float2*>(p) = make_float2(x[2 * q], x[2 * q + 1]);
-            } else {
-                p[0] = x[q];
-            }
+            *reinterpret_cast<float4*>(p) = make_float4(x[4 * q], x[4 * q + 1], x[4 * q + 2], x[4 * q + 3]);
         }
     } else {
 #pragma unroll
@@ -154,26 +197,16 @@ __device__ __forceinline__ void row_zero(float* __restrict__ row, int d, int gl)
 // partner in it gives the same sum) and row_mirror the other half-row --
 // four VALU ops with a DPP operand instead of four ds_bpermute round trips
 // through the LDS crossbar.  Called group-uniformly (no lane of the row is
-// inactive).  CF_DPP_GSUM 0: the xor butterfly on __shfl_xor.
-#ifndef CF_DPP_GSUM
-#define CF_DPP_GSUM 1
-#endif
+// inactive).
 template <int CTRL>
 __device__ __forceinline__ float dpp_f(float v) {
     return __int_as_float(__builtin_amdgcn_mov_dpp(__float_as_int(v), CTRL, 0xF, 0xF, false));
 }
 __device__ __forceinline__ float gsum(float v) {
-#if CF_DPP_GSUM
     v += dpp_f<0xB1>(v);    // quad_perm [1,0,3,2]
     v += dpp_f<0x4E>(v);    // quad_perm [2,3,0,1]
     v += dpp_f<0x141>(v);   // row_half_mirror
     v += dpp_f<0x140>(v);   // row_mirror
-#else
-    v += __shfl_xor(v, 8, 64);
-    v += __shfl_xor(v, 4, 64);
-    v += __shfl_xor(v, 2, 64);
-    v += __shfl_xor(v, 1, 64);
-#endif
     return v;
 }
 
@@ -183,17 +216,10 @@ __device__ __forceinline__ uint32_t dpp_u(uint32_t v) {
 }
 // OR over a 16-lane group (one DPP row), the same steps as gsum
 __device__ __forceinline__ uint32_t gor(uint32_t v) {
-#if CF_DPP_GSUM
     v |= dpp_u<0xB1>(v);
     v |= dpp_u<0x4E>(v);
     v |= dpp_u<0x141>(v);
     v |= dpp_u<0x140>(v);
-#else
-    v |= (uint32_t)__shfl_xor((int)v, 8, 64);
-    v |= (uint32_t)__shfl_xor((int)v, 4, 64);
-    v |= (uint32_t)__shfl_xor((int)v, 2, 64);
-    v |= (uint32_t)__shfl_xor((int)v, 1, 64);
-#endif
     return v;
 }
 
@@ -420,12 +446,6 @@ __device__ __forceinline__ int32_t draw_item(uint64_t key, uint64_t ctr, int64_t
 // The draw runs 8 lanes per pair (32 pairs per block): one wave generation
 // covers a 65,536-pair batch at full occupancy, and a user's row (~51 ids at
 // cfg2) is tested in one batch of up to 8 independent 32-B loads.
-#ifndef CF_PREP_GL
-#define CF_PREP_GL 8       // lanes per pair in the draw (a power of two, 2..16)
-#endif
-#ifndef CF_PREP_CHUNKS
-#define CF_PREP_CHUNKS 8   // row chunks in flight per candidate test
-#endif
 constexpr int kPrepGL = CF_PREP_GL;
 constexpr int kPrepPairsPerBlock = kBlock / kPrepGL;
 constexpr int kPrepChunks = CF_PREP_CHUNKS;
@@ -436,35 +456,14 @@ constexpr int kPrepChunks = CF_PREP_CHUNKS;
 // lanes.  Each lane keeps 64 / 4 = 16 row chunks in flight (one scan covers
 // 64 ids, as the 8-lane group's 8 x 8).  W = 5 keeps 8 lanes: all five
 // negatives' first attempts in one scan.
-#ifndef CF_PREP_GL_W1
-#define CF_PREP_GL_W1 4
-#endif
-#ifndef CF_PREP_CHUNKS_W1
-#define CF_PREP_CHUNKS_W1 (64 / CF_PREP_GL_W1)
-#endif
 __host__ __device__ constexpr int prep_chunks(int pgl) { return pgl == kPrepGL ? kPrepChunks : CF_PREP_CHUNKS_W1; }
-// row scan in 16-B loads (4 ids per lane per chunk): measured SLOWER at cfg2
-// (same box, r03: draw alone 183 vs 119 us, 0.489 vs 0.399 ms/step;
-// profiles/r03/ab_draw_vec_sortw.txt) -- the masked 4 x 8 compare per chunk
-// and the misaligned 128-B spans cost more than the fewer load instructions
-// save; 4-B loads stay the default
-#ifndef CF_PREP_VEC
-#define CF_PREP_VEC 0
-#endif
-#ifndef CF_PREP_VCHUNKS
-#define CF_PREP_VCHUNKS 4 // 128-B row chunks in flight per group (512 ids)
-#endif
-constexpr int kPrepVChunks = CF_PREP_VCHUNKS;
 
 // OR over the PGL lanes of a draw group.  A group of 4 or 8 lanes lies in
 // one DPP row: quad_perm steps OR each quad, row_half_mirror the other quad
-// of an 8-lane group (round 4; CF_DPP_DRAW 0: __shfl_xor)
-#ifndef CF_DPP_DRAW
-#define CF_DPP_DRAW 1
-#endif
+// of an 8-lane group; other widths take the __shfl_xor butterfly
 template <int PGL = kPrepGL>
 __device__ __forceinline__ uint32_t gor8(uint32_t v) {
-    if constexpr (CF_DPP_DRAW && (PGL == 4 || PGL == 8)) {
+    if constexpr (PGL == 4 || PGL == 8) {
         v |= dpp_u<0xB1>(v);   // quad_perm [1,0,3,2]
         v |= dpp_u<0x4E>(v);   // quad_perm [2,3,0,1]
         if constexpr (PGL == 8) v |= dpp_u<0x141>(v);   // row_half_mirror
@@ -478,7 +477,7 @@ __device__ __forceinline__ uint32_t gor8(uint32_t v) {
 // unrolling); a 4-lane group is a quad: quad_perm [k,k,k,k]
 template <int PGL>
 __device__ __forceinline__ int32_t gbcast(int32_t v, int k) {
-    if constexpr (CF_DPP_DRAW && PGL == 4) {
+    if constexpr (PGL == 4) {
         switch (k) {
             case 0: return (int32_t)dpp_u<0x00>((uint32_t)v);
             case 1: return (int32_t)dpp_u<0x55>((uint32_t)v);
@@ -509,42 +508,14 @@ __device__ __forceinline__ bool is_positive(const StepArgs& a, int u, int32_t j)
 }
 
 // Which of the group's candidates cand[0, ncand) lie in the user's sorted
-// CSR row [rb, re) (bit c of the group-OR'ed result).  CF_PREP_VEC: lane gl
-// reads 16 B (4 ids) of every 128-B chunk from the 16-B-aligned start at or
-// before rb, kPrepVChunks chunks in flight -- a 51-id row is two load
-// instructions instead of seven 4-B ones (the indices allocation is padded
-// by 4 ids, so an int4 never leaves it); ids outside [rb, re) never match.
+// CSR row [rb, re) (bit c of the group-OR'ed result): lane gl reads one id
+// of every PGL-id chunk, prep_chunks(PGL) chunks in flight.
 template <int PGL = kPrepGL>
 __device__ __forceinline__ uint32_t row_hits(const int32_t* __restrict__ ind, int64_t rb, int64_t re, int gl,
                                              const int32_t (&cand)[PGL], int ncand) {
     constexpr int kPrepGL = PGL;                   // the group's lanes
     constexpr int kPrepChunks = prep_chunks(PGL);  // chunks in flight per lane
     uint32_t hit = 0;
-#if CF_PREP_VEC
-    constexpr int CW = 4 * kPrepGL;   // ids per chunk
-    const int64_t a0 = rb & ~(int64_t)3;
-    const int nch = (int)((re - a0 + CW - 1) / CW);
-    for (int c0 = 0; c0 < nch; c0 += kPrepVChunks) {
-        int4 el[kPrepVChunks];
-#pragma unroll
-        for (int q = 0; q < kPrepVChunks; ++q) {
-            const int64_t t = a0 + (int64_t)(c0 + q) * CW + 4 * gl;
-            el[q] = (t < re) ? *reinterpret_cast<const int4*>(ind + t) : make_int4(-1, -1, -1, -1);
-        }
-#pragma unroll
-        for (int q = 0; q < kPrepVChunks; ++q) {
-            const int64_t t = a0 + (int64_t)(c0 + q) * CW + 4 * gl;
-            const int32_t e4[4] = {el[q].x, el[q].y, el[q].z, el[q].w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const bool in = t + e >= rb && t + e < re;
-#pragma unroll
-                for (int c = 0; c < kPrepGL; ++c)
-                    hit |= (in && c < ncand && e4[e] == cand[c]) ? (1u << c) : 0u;
-            }
-        }
-    }
-#else
     const int nchunk = (int)((re - rb + kPrepGL - 1) / kPrepGL);
     for (int c0 = 0; c0 < nchunk; c0 += kPrepChunks) {
         int32_t el[kPrepChunks];
@@ -559,7 +530,6 @@ __device__ __forceinline__ uint32_t row_hits(const int32_t* __restrict__ ind, in
             for (int c = 0; c < kPrepGL; ++c)
                 hit |= (c < ncand && el[q] == cand[c]) ? (1u << c) : 0u;
     }
-#endif
     return hit;
 }
 
@@ -578,16 +548,10 @@ __device__ __forceinline__ void prep_body(const StepArgs& a, int block) {
         const uint64_t slot = a.slot_base + (uint64_t)p;
         // shuffled pair order (sampler_ranking.py:24); one 16-B record per pair
         // carries the user's CSR extent, so the row scan does not wait on a
-        // dependent indptr load.  pre_pairs: the record the previous step's
-        // gradient launch fetched (StepArgs::pf_out), read coalesced
-#ifdef CF_EXP_DRAW_NOREC   // attribution only (wrong batches): no record load
-        const int4 pr = make_int4((int)(slot % 1000000), (int)(slot % 100000), (int)((slot * 50) % 40000000), 50);
-#else
-        const int4 pr = a.pre_pairs != nullptr ? a.pre_pairs[p]
-                      : a.order_recs != nullptr ? a.order_recs[slot]
-                      : a.order != nullptr   ? a.pairs[a.order[slot]]
-                                             : a.pairs[permute(slot, a.perm)];
-#endif
+        // dependent indptr load
+        const int4 pr = a.order_recs != nullptr ? a.order_recs[slot]
+                      : a.order != nullptr    ? a.pairs[a.order[slot]]
+                                              : a.pairs[permute(slot, a.perm)];
         u = pr.x;
         i = pr.y;
         key = mix64(a.rng_key ^ (slot * 0xD1B54A32D192ED03ull));
@@ -634,11 +598,7 @@ __device__ __forceinline__ void prep_body(const StepArgs& a, int block) {
     // ranks are stored at the end).  pos_sort: the positive's rank among the
     // batch's positives of i (the negatives count in cntV), psort's key
     int rk_u = 0, rk_i = 0;
-#ifdef CF_EXP_DRAW_NOATOM   // attribution only (wrong ranks): no count atomics
-    if (false) {
-#else
     if (gl == 0) {
-#endif
         if (runs) {
             if (run_rank == 0) {   // the run's first pair in this wave
                 if (run_atomic) run_base = atomicAdd(&a.cntU[u], run_len);
@@ -679,17 +639,13 @@ __device__ __forceinline__ void prep_body(const StepArgs& a, int block) {
             // speculative count of attempt 0 (lane w - w0 < nw holds it), in
             // flight during the scan (StepArgs::spec_ph)
             int rk_s = 0;
-#ifndef CF_EXP_DRAW_NOATOM
             if (spec && gl < nw) rk_s = atomicAdd(&a.cntV[jl], 1);
-#endif
             uint32_t hit = 0;
             {
                 int32_t cand[PGL];
 #pragma unroll
                 for (int k = 0; k < PGL; ++k) cand[k] = gbcast<PGL>(jl, k);
-#ifndef CF_EXP_DRAW_NOSCAN   // attribution only (wrong batches): no row scan
                 hit = gor8<PGL>(row_hits<PGL>(a.indices, rb, re, gl, cand, nl));
-#endif
             }
             // lane w < nw: the first accepted attempt of negative w
             // (the winning lane found from the group-uniform hit mask first:
@@ -761,321 +717,9 @@ __device__ __forceinline__ void prep_body(const StepArgs& a, int block) {
     }
 }
 
-// ---------------------------------------------------------------------------
-// prep, one lane per pair (neg_check = 2): with the Pos(u) set a pair needs no
-// cooperative row scan, so a wave draws 64 pairs at once -- 8x the pairs of
-// the 8-lane groups per wave generation -- and every negative's probes are in
-// flight together.  Same draw sequence as prep_body (negative w takes the
-// first attempt k = 0, 1, .. of draw(key, (w << 32) + k) outside Pos(u)), so
-// the same batches.  Measured SLOWER than the 8-lane groups at every bench
-// config (cfg2 draw 135 vs 118 us, apply + draw 266 vs 232 us; cfg4 apply +
-// draw 100 vs 67 us): 64 scattered probes and returning count atomics per
-// wave instruction serialise in the address path, and 8-lane groups keep
-// more waves -- more independent chains -- in flight.  Kept as an option.
-// ---------------------------------------------------------------------------
-// Built only with -DCF_LANE_DRAW (its registers would otherwise count against
-// every launch that carries a draw branch)
-#ifndef CF_LANE_DRAW
-#define CF_LANE_DRAW 0
-#endif
-__host__ __device__ __forceinline__ bool lane_prep(const StepArgs& a) {
-    return CF_LANE_DRAW && a.lane_draw != 0 && (!a.sample || a.pos_set != nullptr);
-}
-
-template <int MODEL, int WT>
-__device__ __forceinline__ void prep_lane_body(const StepArgs& a, int block) {
-    const int p = block * kBlock + (int)threadIdx.x;
-    if (p >= a.B) return;  // no block barrier below
-    constexpr int NJ = WT > 0 ? WT : 1;
-    const int W = WT > 0 ? WT : a.W;
-    const int G = (MODEL == GBPR) ? a.G : 0;
-    const int B = a.B;
-    int u, i;
-    uint64_t key = 0;
-    if (a.sample) {
-        const uint64_t slot = a.slot_base + (uint64_t)p;
-        const int4 pr = a.order_recs != nullptr ? a.order_recs[slot]
-                      : a.order != nullptr ? a.pairs[a.order[slot]]
-                                           : a.pairs[permute(slot, a.perm)];   // sampler_ranking.py:24
-        u = pr.x;
-        i = pr.y;
-        key = mix64(a.rng_key ^ (slot * 0xD1B54A32D192ED03ull));
-    } else {
-        u = a.occU[p];
-        i = a.occV[p];
-    }
-    int64_t cb = 0, ce = 0;   // GBPR: the item's user column, fetched beside the probes
-    if (MODEL == GBPR && a.sample) {
-        cb = a.indptr_t[i];
-        ce = a.indptr_t[i + 1];
-    }
-    for (int w0 = 0; w0 < W; w0 += NJ) {
-        int32_t j[NJ];
-        if (a.sample) {
-            // negItems = randint(0, n_items), redrawn while j in Pos(u)
-            // (sampler_ranking.py:30-36), every negative's probe chain at once
-            uint64_t ctr[NJ], s[NJ];
-            unsigned long long kk[NJ];
-            uint32_t pend = 0;
-#pragma unroll
-            for (int q = 0; q < NJ; ++q) {
-                ctr[q] = (uint64_t)(w0 + q) << 32;
-                j[q] = draw_item(key, ctr[q]++, a.n_items);
-                kk[q] = ((unsigned long long)(uint32_t)u << 32) | (uint32_t)j[q];
-                s[q] = pos_slot(kk[q], a.pos_mask);
-                pend |= (w0 + q < W) ? (1u << q) : 0u;
-            }
-            while (pend) {
-                unsigned long long t[NJ];
-#pragma unroll
-                for (int q = 0; q < NJ; ++q) t[q] = ((pend >> q) & 1u) ? a.pos_set[s[q]] : kPosEmpty;
-#pragma unroll
-                for (int q = 0; q < NJ; ++q) {
-                    if (!((pend >> q) & 1u)) continue;
-                    if (t[q] == kk[q]) {            // a positive: the next attempt
-                        j[q] = draw_item(key, ctr[q]++, a.n_items);
-                        kk[q] = ((unsigned long long)(uint32_t)u << 32) | (uint32_t)j[q];
-                        s[q] = pos_slot(kk[q], a.pos_mask);
-                    } else if (t[q] == kPosEmpty) { // not in Pos(u): accepted
-                        pend &= ~(1u << q);
-                    } else {                        // another key: probe on
-                        s[q] = (s[q] + 1) & a.pos_mask;
-                    }
-                }
-            }
-#pragma unroll
-            for (int q = 0; q < NJ; ++q)
-                if (w0 + q < W) a.occV[B + (int64_t)p * W + w0 + q] = j[q];
-        } else {
-#pragma unroll
-            for (int q = 0; q < NJ; ++q)
-                if (w0 + q < W) j[q] = a.occV[B + (int64_t)p * W + w0 + q];
-        }
-        if (a.count_items) {
-#pragma unroll
-            for (int q = 0; q < NJ; ++q)
-                if (w0 + q < W) a.rankV[B + (int64_t)p * W + w0 + q] = atomicAdd(&a.cntV[j[q]], 1);
-        }
-    }
-    if (MODEL == GBPR) {
-        for (int k = 0; k < G; ++k) {
-            int32_t g;
-            if (a.sample) {
-                // group = np.random.choice(item_posUserList[i], gsize) (sampler_gbpr.py:41)
-                const uint64_t h = mix64(key + ((uint64_t)(kMaxNeg + k) << 32));
-                g = a.indices_t[cb + (int64_t)uniform_below(h, (uint64_t)(ce - cb))];
-                g = (g >= a.shard_u0 && g < a.shard_u1) ? g - a.shard_u0 : -1 - g;
-                a.occU[B + (int64_t)p * G + k] = g;
-            } else {
-                g = a.occU[B + (int64_t)p * G + k];
-            }
-            if (a.count_users && g >= 0) a.rankU[B + (int64_t)p * G + k] = atomicAdd(&a.cntU[g], 1);
-        }
-    }
-    if (a.sample) {
-        a.occU[p] = u;
-        a.occV[p] = i;
-    }
-    if (a.count_users) a.rankU[p] = atomicAdd(&a.cntU[u], 1);
-    if (a.count_items) a.rankV[p] = atomicAdd(&a.cntV[i], 1);
-}
-
-// ---------------------------------------------------------------------------
-// the device draw with NP pairs per 8-lane group (CF_PREP_PAIRS): the draw is
-// latency-bound (pair record -> row scan -> returning count atomics), so a
-// group carries NP pairs' chains at once -- both pairs' records, then both
-// row scans' chunks, then both pairs' atomics in flight together.  Same
-// candidates, acceptance rule and counts as prep_body (the same batches).
-// Device sampler with the CSR row scan and W <= the group width only;
-// everything else takes prep_body.  Measured SLOWER at cfg2 (same box, r03:
-// draw alone 130 vs 120 us, apply + draw 199 vs 190 us, step 0.408 vs 0.3995
-// ms; profiles/r03/ab_draw_pairs.txt): the draw is not short of chains in
-// flight per wave -- its returning count atomics and the row-scan requests
-// bound it -- so one pair per group stays the default; -DCF_PREP_PAIRS=2
-// builds the variant.
-// ---------------------------------------------------------------------------
-#ifndef CF_PREP_PAIRS
-#define CF_PREP_PAIRS 1
-#endif
-constexpr int kPrepPairs = CF_PREP_PAIRS;
-
-__host__ __device__ __forceinline__ bool multi_prep(const StepArgs& a) {
-    return kPrepPairs > 1 && a.sample && a.pos_set == nullptr && a.W <= kPrepGL && !lane_prep(a);
-}
-
-template <int MODEL>
-__device__ __forceinline__ void prep_body_np(const StepArgs& a, int block) {
-    constexpr int PGL = kPrepGL, NP = kPrepPairs;
-    const int gl = threadIdx.x & (PGL - 1);
-    const int grp = threadIdx.x / PGL;
-    const int W = a.W, B = a.B;
-    const int G = (MODEL == GBPR) ? a.G : 0;
-    const int nw = W, C = PGL / nw, nl = C * nw;
-    int p[NP], u[NP], i[NP], nchunk[NP];
-    bool ok[NP];
-    uint64_t key[NP];
-    int64_t rb[NP], re[NP];
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-        p[k] = (block * NP + k) * kPrepPairsPerBlock + grp;
-        ok[k] = p[k] < B;   // group-uniform
-    }
-    if (!ok[0]) return;    // (p[k] grows with k) whole group leaves; no block barrier below
-    // pair records (one 16-B load each, all in flight)
-    int4 pr[NP];
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-        const uint64_t slot = a.slot_base + (uint64_t)p[k];
-        key[k] = mix64(a.rng_key ^ (slot * 0xD1B54A32D192ED03ull));
-        if (ok[k]) pr[k] = a.order_recs != nullptr ? a.order_recs[slot]
-                         : a.order != nullptr ? a.pairs[a.order[slot]]
-                                              : a.pairs[permute(slot, a.perm)];   // sampler_ranking.py:24
-    }
-    int maxchunk = 0;
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-        u[k] = ok[k] ? pr[k].x : 0;
-        i[k] = ok[k] ? pr[k].y : 0;
-        rb[k] = ok[k] ? (int64_t)(uint32_t)pr[k].z : 0;
-        re[k] = ok[k] ? rb[k] + pr[k].w : 0;
-        nchunk[k] = (int)((re[k] - rb[k] + PGL - 1) / PGL);
-        maxchunk = nchunk[k] > maxchunk ? nchunk[k] : maxchunk;
-    }
-    // negItems = randint(0, n_items), redrawn while j in Pos(u)
-    // (sampler_ranking.py:30-36): lane l holds attempt l / nw of negative
-    // l % nw; every pair's first C attempts are tested in one row scan
-    int32_t jl[NP];
-    uint32_t hit[NP];
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-        jl[k] = (gl < nl) ? draw_item(key[k], ((uint64_t)(gl % nw) << 32) + (uint64_t)(gl / nw), a.n_items) : -1;
-        hit[k] = 0u;
-    }
-    {
-        int32_t cand[NP][PGL];
-#pragma unroll
-        for (int k = 0; k < NP; ++k)
-#pragma unroll
-            for (int c = 0; c < PGL; ++c) cand[k][c] = gbcast<PGL>(jl[k], c);
-        for (int c0 = 0; c0 < maxchunk; c0 += kPrepChunks) {
-            int32_t el[NP][kPrepChunks];
-#pragma unroll
-            for (int k = 0; k < NP; ++k)
-#pragma unroll
-                for (int q = 0; q < kPrepChunks; ++q) {
-                    const int64_t t = rb[k] + (int64_t)(c0 + q) * PGL + gl;
-                    el[k][q] = (t < re[k]) ? a.indices[t] : -1;
-                }
-#pragma unroll
-            for (int k = 0; k < NP; ++k)
-#pragma unroll
-                for (int q = 0; q < kPrepChunks; ++q)
-#pragma unroll
-                    for (int c = 0; c < PGL; ++c)
-                        hit[k] |= (c < nl && el[k][q] == cand[k][c]) ? (1u << c) : 0u;
-        }
-    }
-    int32_t j[NP];
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-        hit[k] = gor8(hit[k]);
-        // lane w < nw: the first accepted attempt of negative w
-        bool done = false;
-        j[k] = -1;
-        for (int c = 0; c < C; ++c) {
-            const int src = c * nw + (gl % nw);
-            const int32_t cv = __shfl(jl[k], src, PGL);
-            if (!done && gl < nw && !((hit[k] >> src) & 1u)) {
-                j[k] = cv;
-                done = true;
-            }
-        }
-        // rare: every tested attempt of some negative was a positive ->
-        // continue its sequence at attempt C, one candidate per lane
-        uint32_t pending = gor8((ok[k] && gl < nw && !done) ? (1u << gl) : 0u);
-        uint64_t ctr = ((uint64_t)gl << 32) + (uint64_t)C;
-        if ((pending >> gl) & 1u) j[k] = draw_item(key[k], ctr++, a.n_items);
-        while (pending != 0u) {  // group-uniform
-            int32_t cand[PGL];
-#pragma unroll
-            for (int c = 0; c < PGL; ++c) cand[c] = gbcast<PGL>(j[k], c);
-            uint32_t h2 = 0;
-            for (int c0 = 0; c0 < nchunk[k]; c0 += kPrepChunks) {
-                int32_t el[kPrepChunks];
-#pragma unroll
-                for (int q = 0; q < kPrepChunks; ++q) {
-                    const int64_t t = rb[k] + (int64_t)(c0 + q) * PGL + gl;
-                    el[q] = (t < re[k]) ? a.indices[t] : -1;
-                }
-#pragma unroll
-                for (int q = 0; q < kPrepChunks; ++q)
-#pragma unroll
-                    for (int c = 0; c < PGL; ++c)
-                        h2 |= (c < nw && el[q] == cand[c]) ? (1u << c) : 0u;
-            }
-            h2 = gor8(h2) & pending;
-            if ((h2 >> gl) & 1u) j[k] = draw_item(key[k], ctr++, a.n_items);
-            pending = h2;
-        }
-    }
-    // occurrences and their ranks (returning count atomics), every pair's at once
-    int32_t rj[NP], ru[NP], ri[NP];
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-        if (ok[k] && gl < nw) {
-            a.occV[B + p[k] * W + gl] = j[k];
-            if (a.count_items) rj[k] = atomicAdd(&a.cntV[j[k]], 1);
-        }
-        if (ok[k] && gl == 0) {
-            a.occU[p[k]] = u[k];
-            a.occV[p[k]] = i[k];
-            if (a.count_users) ru[k] = atomicAdd(&a.cntU[u[k]], 1);
-            // pos_sort: the positive's rank among the batch's positives of i
-            if (a.count_items) ri[k] = atomicAdd(a.cntP != nullptr ? &a.cntP[i[k]] : &a.cntV[i[k]], 1);
-        }
-    }
-#pragma unroll
-    for (int k = 0; k < NP; ++k) {
-        if (ok[k] && gl < nw && a.count_items) a.rankV[B + p[k] * W + gl] = rj[k];
-        if (ok[k] && gl == 0) {
-            if (a.count_users) a.rankU[p[k]] = ru[k];
-            if (a.count_items) a.rankV[p[k]] = ri[k];
-        }
-    }
-    if (MODEL == GBPR) {
-#pragma unroll
-        for (int k = 0; k < NP; ++k) {
-            if (!ok[k]) continue;
-            for (int q = gl; q < G; q += PGL) {
-                // group = np.random.choice(item_posUserList[i], gsize) (sampler_gbpr.py:41)
-                const int64_t cb = a.indptr_t[i[k]], ce = a.indptr_t[i[k] + 1];
-                const uint64_t h = mix64(key[k] + ((uint64_t)(kMaxNeg + q) << 32));
-                int32_t g = a.indices_t[cb + (int64_t)uniform_below(h, (uint64_t)(ce - cb))];
-                g = (g >= a.shard_u0 && g < a.shard_u1) ? g - a.shard_u0 : -1 - g;
-                a.occU[B + p[k] * G + q] = g;
-                if (a.count_users && g >= 0) a.rankU[B + p[k] * G + q] = atomicAdd(&a.cntU[g], 1);
-            }
-        }
-    }
-}
-
-// the draw + count of one block of a step's batch: one lane per pair when no
-// row scan is needed (lane_prep), several pairs per 8-lane group on the
-// device sampler's row scan (multi_prep), else prep_body
+// the draw + count of one block of a step's batch
 template <int MODEL>
 __device__ __forceinline__ void prep_any(const StepArgs& a, int block) {
-#if CF_LANE_DRAW
-    if (lane_prep(a)) {
-        if (a.W == 1) prep_lane_body<MODEL, 1>(a, block);
-        else if (a.W == 5) prep_lane_body<MODEL, 5>(a, block);
-        else prep_lane_body<MODEL, 0>(a, block);
-        return;
-    }
-#endif
-    if (multi_prep(a)) {
-        prep_body_np<MODEL>(a, block);
-        return;
-    }
     if (a.W == 1)
         prep_body<MODEL, CF_PREP_GL_W1>(a, block);
     else
@@ -1083,8 +727,7 @@ __device__ __forceinline__ void prep_any(const StepArgs& a, int block) {
 }
 
 __host__ __device__ __forceinline__ int prep_pairs_per_block(const StepArgs& a) {
-    return lane_prep(a) ? kBlock : multi_prep(a) ? kPrepPairs * kPrepPairsPerBlock
-                                 : a.W == 1 ? kBlock / CF_PREP_GL_W1 : kPrepPairsPerBlock;
+    return a.W == 1 ? kBlock / CF_PREP_GL_W1 : kPrepPairsPerBlock;
 }
 
 template <int MODEL>
@@ -1530,41 +1173,10 @@ __device__ __forceinline__ void grad_body(const StepArgs& a, int block) {
 // so that the latency-bound draw fills the gaps of the gather.  np == 0 is the
 // plain gradient launch.
 __device__ __forceinline__ bool minor_block(int b, int nmajor, int nminor, int& idx) {
-#ifdef CF_GRAD_PREP_TAIL  // experiment: the draw blocks after every gradient block
-    if (b >= nmajor) {
-        idx = b - nmajor;
-        return true;
-    }
-    idx = b;
-    return false;
-#endif
     const int64_t tot = (int64_t)nmajor + nminor;
     const int lo = (int)(((int64_t)b * nminor) / tot);
     const int hi = (int)(((int64_t)(b + 1) * nminor) / tot);
     idx = (hi > lo) ? lo : b - lo;
-    return hi > lo;
-}
-
-// The same with the minor blocks front-loaded (experiment, CF_APPLY_DRAW_SKEW):
-// the number of minor blocks before block b is F(b) = nminor - floor(nminor
-// (tot - b)^2 / tot^2), whose slope falls from 2 nminor / tot to 0, so the
-// latency-bound draw starts first and the bandwidth-bound apply blocks form
-// the tail.  Needs nminor <= nmajor (slope <= 1: at most one minor block per
-// block id); otherwise the even spread.
-// BACK: the mirror image, F(b) = floor(nminor b^2 / tot^2): the draw blocks
-// thin at the start and dense at the end (the apply's bandwidth first).
-template <bool BACK = false>
-__device__ __forceinline__ bool minor_block_front(int b, int nmajor, int nminor, int& idx) {
-    if (nminor > nmajor) return minor_block(b, nmajor, nminor, idx);
-    const int64_t tot = (int64_t)nmajor + nminor;
-    auto F = [&](int64_t x) {
-        // x^2 nminor <= tot^3 < 2^63 for tot < 2^21
-        if (BACK) return (x * x * (int64_t)nminor) / (tot * tot);
-        const int64_t r = tot - x;
-        return (int64_t)nminor - (r * r * (int64_t)nminor) / (tot * tot);
-    };
-    const int64_t lo = F(b), hi = F((int64_t)b + 1);
-    idx = (int)((hi > lo) ? lo : (int64_t)b - lo);
     return hi > lo;
 }
 
@@ -1594,12 +1206,6 @@ __device__ __forceinline__ void gload_acc(const float* __restrict__ A, int64_t r
                                           bool want, float (&acc)[EPL]) {
 #pragma unroll
     for (int s = 0; s < EPL; ++s) acc[s] = 1.f;
-#ifdef CF_EXP_NO_ACC
-    want = false;
-#endif
-#ifdef CF_EXP_ACC_ALWAYS  // issue the accumulator rows with the table rows (no dependent phase)
-    want = true;
-#endif
     if (want) row_ld<EPL>(A + r * (int64_t)d, d, gl, 1.f, acc);
 }
 
@@ -1632,25 +1238,20 @@ __device__ __forceinline__ void gfinish_pre(float* __restrict__ X, float* __rest
                                             int64_t r, int count, int64_t slot, int d, int gl,
                                             const float (&x0)[EPL], const float (&acc0)[EPL],
                                             const float (&g)[EPL], const StepArgs& a) {
-    // CF_EXP_* are bench-only attribution builds (wrong results by design)
     if (count == 1) {
         if (a.items_grad_only && X == a.V) {
             gstore<EPL>(G, r, d, gl, g);  // sole writer of the zeroed dense row
         } else {
-#ifndef CF_EXP_NO_SINGLE
             gapply_pre<EPL>(X, A, r, d, gl, x0, acc0, g, a.lr, a.clip != 0, a.clip_norm);
-#endif
         }
         if (gl == 0) cnt[r] = 0;
     } else if (slot >= 0) {
         gstore<EPL>(S, slot, d, gl, g);
     } else {
-#ifndef CF_EXP_NO_ATOMIC
         if (a.GU64 != nullptr && X == a.U)   // deterministic pos_sort: a user past its slot cap
             fx_atomic<EPL>(a.GU64 + (int64_t)a.hotU[r] * d, d, gl, g, a.fx_bad);
         else
             gatomic<EPL>(acc_of(G, slot, a), r, d, gl, g);
-#endif
         if (a.items_grad_only && a.capV == 0 && X == a.V && gl == 0) cnt[r] = 0;  // see gfinish
     }
 }
@@ -2035,26 +1636,6 @@ __device__ __forceinline__ void grad_fast_body(const StepArgs& a, int block) {
         pp[k] = (block * P + k) * GPB + grp;
         ok[k] = pp[k] < a.B;
     }
-    // pair-record prefetch for the next step (StepArgs::pf_out): issued
-    // first, stored last, so its latency hides under this block's pairs
-    int4 pfr = make_int4(0, 0, 0, 0);
-    int64_t pfp = -1;
-#ifndef CF_PAIR_PREFETCH
-// 1: the prefetch compiled in.  Its registers take grad_sort_kernel<BPR, 4, 1>
-// from 75 to 81 VGPRs, 6 -> 5 waves / SIMD: the cfg2 gradient launch ran
-// 197.3 us with it, 179.9 us without (same box, round 4,
-// profiles/r04/ab_occupancy/ab_r04_ab1.txt); the engine refuses the option unless built in
-#define CF_PAIR_PREFETCH 0
-#endif
-    if constexpr (SORT && CF_PAIR_PREFETCH) {
-        if (a.pf_out != nullptr && gl == 0) {
-            const int64_t q = (int64_t)block * GPB + grp;
-            if (q < a.pf_B) {
-                pfp = q;
-                pfr = a.pairs[permute(a.pf_slot_base + (uint64_t)q, a.pf_perm)];
-            }
-        }
-    }
 #pragma unroll
     for (int k = 0; k < P; ++k)
         if (ok[k]) {
@@ -2112,19 +1693,11 @@ __device__ __forceinline__ void grad_fast_body(const StepArgs& a, int block) {
         for (int k = 0; k < GPB; ++k) t += s_loss[k];
         a.loss_partial[block] = t;
     }
-    if constexpr (SORT && CF_PAIR_PREFETCH) {
-        if (pfp >= 0) a.pf_out[pfp] = pfr;
-    }
 }
 
 // FULL (round 5): as grad_sort_kernel's, for the phased kernel without draw
 // blocks -- cfg2 at SURVEY's B = 65,536 (pos_sort off) runs this one
 template <int MODEL, int EPL, int WT, int P, bool DRAW, bool SORT = false, bool FULL = false>
-#ifdef CF_GRAD_WAVES_PER_EU
-#define CF_GRAD_ATTR __attribute__((amdgpu_waves_per_eu(CF_GRAD_WAVES_PER_EU, 8)))
-#else
-#define CF_GRAD_ATTR
-#endif
 __global__ __launch_bounds__(kBlock) CF_GRAD_ATTR void grad_fast_kernel(StepArgs a, StepArgs nx, int ng, int np) {
     if constexpr (FULL) __builtin_assume(a.d == kGL * EPL);
     int idx = blockIdx.x;
@@ -2138,28 +1711,8 @@ __global__ __launch_bounds__(kBlock) CF_GRAD_ATTR void grad_fast_kernel(StepArgs
 // register budget can be set apart from the other phased instantiations:
 // CF_SORT_MIN_WAVES = minimum waves per SIMD (8 = at most 64 VGPRs).  8 was
 // measured SLOWER at cfg2 (gradient launch 236 vs 179 us: the 74-VGPR body
-// spills), so the budget is left to the compiler (6 waves/SIMD)
-#ifndef CF_SORT_MIN_WAVES
-#define CF_SORT_MIN_WAVES 1
-#endif
-#ifndef CF_ASSUME_FULL_ROWS
-#define CF_ASSUME_FULL_ROWS 1
-#endif
-#ifndef CF_ASSUME_FULL_FAST
-#define CF_ASSUME_FULL_FAST 1   // grad_fast_kernel's FULL instantiation at d = 64 (round 5)
-#endif
-// the same for apply_ps_kernel: measured even at cfg2/4/5 (round 4) -- the
-// apply hoists more loads (79 -> 92 VGPRs, one wave per SIMD less), off
-#ifndef CF_ASSUME_FULL_APPLY
-#define CF_ASSUME_FULL_APPLY 0
-#endif
-// CF_SORT_TILES positive-sorted tiles per block (grad_fast_body)
-#ifndef CF_SORT_TILES
-#define CF_SORT_TILES 1
-#endif
-#ifndef CF_SORT_XCD
-#define CF_SORT_XCD 1   // round 5: XCD-contiguous sorted tiles (cfg2 gradient 170 -> 163 us, profiles/r05/ab)
-#endif
+// spills), so the budget is left to the compiler (6 waves/SIMD).
+// CF_SORT_TILES positive-sorted tiles per block (grad_fast_body).
 // DRAW (round 5, pipeline 3): the launch also carries the draw + count blocks
 // of step s+1 (other buffer set), interleaved with the gradient blocks -- the
 // draw is latency-bound, the gradient launch waits on memory 59 % of its
@@ -2179,25 +1732,16 @@ __global__ __launch_bounds__(kBlock, CF_SORT_MIN_WAVES) void grad_sort_kernel(St
             return;
         }
     }
-#if CF_SORT_XCD
     // XCD-contiguous tiles: workgroups are dealt round-robin over the 8 XCDs
     // (b and b + 8 share one), so XCD x takes the contiguous run of sorted
     // tiles [x * full + min(x, rem), ...) -- a Zipf-head positive item whose
-    // run spans many tiles is then gathered through one XCD's L2
+    // run spans many tiles is then gathered through one XCD's L2 (cfg2
+    // gradient 170 -> 163 us, profiles/r05/ab)
     if constexpr (!DRAW) {
         const int nb = (int)gridDim.x, full = nb >> 3, rem = nb & 7, x = idx & 7;
         idx = x * full + (x < rem ? x : rem) + (idx >> 3);
     }
-#endif
     grad_fast_body<MODEL, EPL, WT, CF_SORT_TILES, kGroupsPerBlock, true, FX>(a, idx);
-}
-
-// the same gradient blocks at one wave per workgroup (no draw blocks): a
-// finer dispatch granule, so the last round of workgroups leaves less of the
-// chip idle (a step's gradient launch is only ~2.7 rounds of 256-lane blocks)
-template <int MODEL, int EPL, int WT, int P>
-__global__ __launch_bounds__(kWave) void grad_fast_wave_kernel(StepArgs a) {
-    grad_fast_body<MODEL, EPL, WT, P, kWave / kGL>(a, blockIdx.x);
 }
 
 // ---------------------------------------------------------------------------
@@ -2301,23 +1845,10 @@ __device__ __forceinline__ void pacc_ld(const float* __restrict__ A, int64_t r, 
 
 // minimum waves per SIMD the LDS-staged kernel is built for (1 = the
 // compiler's register budget; LDS alone allows 4)
-#ifndef CF_LDS_WAVES
-#define CF_LDS_WAVES 1
-#endif
-#ifndef CF_LDS_WAVES_GBPR
-#define CF_LDS_WAVES_GBPR 1   // 4 (with CF_LDS_STAGE_ACC: 128 VGPRs, 12-B spill) measured slower (r04j)
-#endif
 #define CF_LDS_ATTR __attribute__((amdgpu_waves_per_eu(MODEL == GBPR ? CF_LDS_WAVES_GBPR : CF_LDS_WAVES, 8)))
-// one negative's LDS reads are not hoisted above the previous negative's
-// terms (the scheduler would otherwise keep all five rows live)
-#ifndef CF_LDS_FENCE
-#define CF_LDS_FENCE 1
-#endif
-#if CF_LDS_FENCE
-#define CF_LDS_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
-#else
-#define CF_LDS_SCHED_FENCE() ((void)0)
-#endif
+// (the __builtin_amdgcn_sched_barrier(0) in the kernel's loops: one negative's
+// LDS reads are not hoisted above the previous negative's terms -- the
+// scheduler would otherwise keep all five rows live)
 // EPL = 8 (d = 128): BPR / AMF / CML, 40 KB of staged rows per block, a
 // negative's accumulator loaded where it is finished (rows seen once are rare
 // at 100K items).  EPL = 4 (d = 64): GBPR at G = 1 (cfg4), 20 KB per block;
@@ -2334,14 +1865,6 @@ __global__ __launch_bounds__(kBlock) CF_LDS_ATTR void grad_lds_kernel(StepArgs a
     static_assert(MODEL == BPR || MODEL == AMF || MODEL == CML || MODEL == GBPR, "no tuples here");
     // 40 KB (d = 128) / 20 KB (d = 64) per block; the loss partials reuse it
     __shared__ float s_v[kGroupsPerBlock * WT * ROW];
-    // GBPR (ACC_EARLY): the negatives' accumulator rows staged the same way
-    // (round 4) instead of held in 20 VGPRs -- 40 KB per block, four blocks per
-    // CU, and the registers for four waves per SIMD
-#ifndef CF_LDS_STAGE_ACC
-#define CF_LDS_STAGE_ACC 0   // 1 measured slower at cfg4 (131.6 vs 126.2 us with 4 waves, 12-B spill; r04j)
-#endif
-    constexpr bool STAGE_ACC = ACC_EARLY && CF_LDS_STAGE_ACC;
-    __shared__ float s_a[STAGE_ACC ? kGroupsPerBlock * WT * ROW : 1];
     const int lane = threadIdx.x & (kWave - 1);
     const int gl = threadIdx.x & (kGL - 1);
     const int grp = threadIdx.x >> 4;
@@ -2389,9 +1912,7 @@ __global__ __launch_bounds__(kBlock) CF_LDS_ATTR void grad_lds_kernel(StepArgs a
         for (int w = 0; w < WT; ++w)
             if (gl == w) jsel = j[w];
         float* wbase = s_v + (threadIdx.x >> 6) * RPW * ROW;
-        float* abase = s_a + (STAGE_ACC ? (threadIdx.x >> 6) * RPW * ROW : 0);
         const int c4 = (lane % LPR) * 4;
-        const bool stage_acc = STAGE_ACC && !a.items_grad_only;
 #pragma unroll
         for (int k = 0; k < RPW / RPI; ++k) {
             const int r = RPI * k + lane / LPR;
@@ -2401,12 +1922,6 @@ __global__ __launch_bounds__(kBlock) CF_LDS_ATTR void grad_lds_kernel(StepArgs a
                 __builtin_amdgcn_global_load_lds(
                     (const __attribute__((address_space(1))) void*)(a.V + (int64_t)jj * d + c4),
                     (__attribute__((address_space(3))) void*)(wbase + RPI * k * ROW), 16, 0, 0);
-            // every negative's accumulator row (at 1M items nearly all are
-            // their row's only occurrence; no count is needed to issue it)
-            if (stage_acc && jj >= 0)
-                __builtin_amdgcn_global_load_lds(
-                    (const __attribute__((address_space(1))) void*)(a.AV + (int64_t)jj * d + c4),
-                    (__attribute__((address_space(3))) void*)(abase + RPI * k * ROW), 16, 0, 0);
         }
     }
     // counts and the u / i rows, then slots and the accumulator rows of the
@@ -2437,7 +1952,7 @@ __global__ __launch_bounds__(kBlock) CF_LDS_ATTR void grad_lds_kernel(StepArgs a
     // slot rows as int32 (n_users * capU and n_items * capV < 2^31 wherever
     // this kernel runs: 10M x 2, 1M x 32 at cfg4): 8 VGPRs fewer than int64
     int32_t su = -1, si = -1, sg = -1, sj[WT];
-    float au[EPL], ai[EPL], ag[MODEL == GBPR ? EPL : 1], aje[ACC_EARLY && !STAGE_ACC ? WT : 1][EPL];
+    float au[EPL], ai[EPL], ag[MODEL == GBPR ? EPL : 1], aje[ACC_EARLY ? WT : 1][EPL];
     float abi = 0.f, abj[WT];   // GBPR: bias accumulators of rows seen once
     const bool item_acc = !a.items_grad_only;
 #pragma unroll
@@ -2456,7 +1971,7 @@ __global__ __launch_bounds__(kBlock) CF_LDS_ATTR void grad_lds_kernel(StepArgs a
 #pragma unroll
             for (int w = 0; w < WT; ++w) abj[w] = (item_acc && cj[w] == 1) ? a.Ab[j[w]] : 0.f;
         }
-        if constexpr (ACC_EARLY && !STAGE_ACC) {
+        if constexpr (ACC_EARLY) {
 #pragma unroll
             for (int w = 0; w < WT; ++w) pacc_ld<EPL>(a.AV, j[w], d, gl, par, item_acc && cj[w] == 1, aje[w]);
         }
@@ -2521,7 +2036,7 @@ __global__ __launch_bounds__(kBlock) CF_LDS_ATTR void grad_lds_kernel(StepArgs a
             pifinish<EPL>(a, i, ci, si, p, sc, a.reg, 0, gl, par, vi, ai, gi);
 #pragma unroll
             for (int w = 0; w < WT; ++w) {
-                CF_LDS_SCHED_FENCE();
+                __builtin_amdgcn_sched_barrier(0);
                 float vj[EPL], aj[EPL], gj[EPL];
                 pacc_ld<EPL>(a.AV, j[w], d, gl, par, item_acc && cj[w] == 1, aj);
                 prow_ld<EPL>(sv + w * ROW, gl, par, vj);
@@ -2539,7 +2054,7 @@ __global__ __launch_bounds__(kBlock) CF_LDS_ATTR void grad_lds_kernel(StepArgs a
             int imp = 0;
 #pragma unroll
             for (int w = 0; w < WT; ++w) {
-                CF_LDS_SCHED_FENCE();
+                __builtin_amdgcn_sched_barrier(0);
                 float t[EPL];
                 prow_ld<EPL>(sv + w * ROW, gl, par, t);
 #pragma unroll
@@ -2566,7 +2081,7 @@ __global__ __launch_bounds__(kBlock) CF_LDS_ATTR void grad_lds_kernel(StepArgs a
             for (int w = 0; w < WT; ++w) {
                 const float share = (dn[w] == m) ? 1.f / cnt : 0.f;
                 const float coef = 2.f * aa * share;
-                CF_LDS_SCHED_FENCE();
+                __builtin_amdgcn_sched_barrier(0);
                 float vj[EPL], gj[EPL], aj[EPL];
                 pacc_ld<EPL>(a.AV, j[w], d, gl, par, item_acc && cj[w] == 1, aj);
                 prow_ld<EPL>(sv + w * ROW, gl, par, vj);
@@ -2637,21 +2152,13 @@ __global__ __launch_bounds__(kBlock) CF_LDS_ATTR void grad_lds_kernel(StepArgs a
             pifinish<EPL>(a, i, ci, si, p, sc, a.reg, 1, gl, par, vi, ai, gi);
 #pragma unroll
             for (int w = 0; w < WT; ++w) {
-                CF_LDS_SCHED_FENCE();
+                __builtin_amdgcn_sched_barrier(0);
                 float vj[EPL], gj[EPL];
                 prow_ld<EPL>(sv + w * ROW, gl, par, vj);
 #pragma unroll
                 for (int s = 0; s < EPL; ++s) gj[s] = -cw[w] * uu[s];   // no L2 on V[j] (gbprmf.py:59-64)
                 if (gl == 0) bias_finish_pre(a, j[w], cj[w], -cw[w] + a.reg * bj[w], sj[w], bj[w], abj[w]);
-                if constexpr (STAGE_ACC) {
-                    float aj[EPL];
-#pragma unroll
-                    for (int s = 0; s < EPL; ++s) aj[s] = 1.f;
-                    if (item_acc && cj[w] == 1) prow_ld<EPL>(s_a + grp * WT * ROW + w * ROW, gl, par, aj);
-                    pifinish<EPL>(a, j[w], cj[w], sj[w], p, -cw[w], 0.f, 0, gl, par, vj, aj, gj);
-                } else {
-                    pifinish<EPL>(a, j[w], cj[w], sj[w], p, -cw[w], 0.f, 0, gl, par, vj, aje[ACC_EARLY ? w : 0], gj);
-                }
+                pifinish<EPL>(a, j[w], cj[w], sj[w], p, -cw[w], 0.f, 0, gl, par, vj, aje[ACC_EARLY ? w : 0], gj);
             }
         }
     }
@@ -2750,9 +2257,6 @@ __device__ __forceinline__ void apply_row(const ApplyArgs& a, int64_t r, bool is
     const int ns = flagged ? 0 : (off != nullptr || local < cap) ? local : cap;
 #pragma unroll
     for (int s = 0; s < EPL; ++s) g[s] = 0.f;
-#ifndef CF_APPLY_NF
-#define CF_APPLY_NF 4
-#endif
     constexpr int NF = CF_APPLY_NF;  // slot rows in flight, summed in rank order (8: occupancy 5, slower)
     // slots [0, ns) in rank order -- or, in deterministic mode for a row of
     // >= 2 whole 64-slot tiles, the head before its first whole tile, the
@@ -2880,9 +2384,6 @@ __device__ __forceinline__ void rows_sum(const float* __restrict__ S, int64_t s0
     }
 }
 
-#ifndef CF_APPLY_NF_PS
-#define CF_APPLY_NF_PS 8   // rows in flight per group in the pos_sort item apply
-#endif
 template <int EPL, bool FX = false>
 __device__ __forceinline__ void apply_item_ps(const ApplyArgs& a, int64_t r, int gl, int cn, int cp, int o,
                                               int on) {
@@ -3117,25 +2618,13 @@ __device__ __forceinline__ void apply_rows_item_block(const ApplyArgs& a, int bl
 // round 4): the apply is bandwidth-bound (~4.9 TB/s), the draw latency-bound
 // (~1 TB/s), and with the draw after every apply block the two overlapped
 // for only ~16 us of a 187 us launch at cfg2 (apply 84 us and draw 119 us
-// as separate launches).  -DCF_APPLY_DRAW_TAIL=1: the old order.
-#ifndef CF_APPLY_DRAW_TAIL
-#define CF_APPLY_DRAW_TAIL 0
-#endif
-#ifndef CF_APPLY_DRAW_SKEW
-// 1: the draw blocks front-loaded (minor_block_front): cfg2 apply + draw 141
-// -> 163 us, B = 65,536 0.0699 -> 0.0783 ms/step (same box, r06k), slower;
-// 2: back-loaded, 155 vs 140 us (r06k2), slower too; 0: evenly interleaved
-#define CF_APPLY_DRAW_SKEW 0
-#endif
-// minimum waves per SIMD the pos_sort apply is built for: 7 (72 VGPRs, 12-B
-// spill) measured even-to-slower at cfg2 (round 4, profiles/r04/ab/ab_r04w_occupancy.txt)
-#ifndef CF_APPLY_MIN_WAVES
-#define CF_APPLY_MIN_WAVES 1
-#endif
-template <int EPL, bool DRAW, bool PS = true, bool FX = false, bool FULL = false>
+// as separate launches).  CF_APPLY_DRAW_TAIL 1 is that old order: its arm is
+// the last one below, which the compiler cannot prove unreachable, so the
+// fused instantiations carry it.
+// CF_APPLY_MIN_WAVES = minimum waves per SIMD: 7 (72 VGPRs, 12-B spill)
+// measured even-to-slower at cfg2 (round 4, profiles/r04/ab/ab_r04w_occupancy.txt)
+template <int EPL, bool DRAW, bool PS = true, bool FX = false>
 __global__ __launch_bounds__(kBlock, CF_APPLY_MIN_WAVES) void apply_ps_kernel(ApplyArgs p, StepArgs nx, int nbI, int nbW) {
-    // FULL: full rows (d == 16 EPL), the `e < d` guards fold away (grad_sort_kernel)
-    if constexpr (FULL) __builtin_assume(p.d == kGL * EPL);
     int b = blockIdx.x;
     if (blockIdx.x == 0 && p.loss_acc != nullptr) fold_loss<kBlock>(p);
     // the compact GU64 rows of this batch are handed out again by the next psort
@@ -3143,9 +2632,7 @@ __global__ __launch_bounds__(kBlock, CF_APPLY_MIN_WAVES) void apply_ps_kernel(Ap
     if constexpr (DRAW && !CF_APPLY_DRAW_TAIL) {
         int idx;
         const int nmin = (int)gridDim.x - nbI - nbW;
-        if (CF_APPLY_DRAW_SKEW == 1   ? minor_block_front<false>(blockIdx.x, nbI + nbW, nmin, idx)
-            : CF_APPLY_DRAW_SKEW == 2 ? minor_block_front<true>(blockIdx.x, nbI + nbW, nmin, idx)
-                                      : minor_block(blockIdx.x, nbI + nbW, nmin, idx)) {
+        if (minor_block(blockIdx.x, nbI + nbW, nmin, idx)) {
             prep_any<BPR>(nx, idx);
             return;
         }
@@ -3234,25 +2721,16 @@ __global__ __launch_bounds__(kBlock) void det_hot_kernel(HotArgs h) {
     }
 }
 
-
-#ifndef CF_APPLY_DETECT_WAVES
-#define CF_APPLY_DETECT_WAVES 1   // 4 measured slower: ~46 owners per block, ~3 per group in series
-#endif
-// waves of an apply block that find owners (kApplyChunk work items each)
+// waves of an apply block that find owners (4 measured slower: ~46 owners per
+// block, ~3 per group in series), kApplyChunk work items each (<= 64.  A/B at
+// cfg2: 64 best; 32 and 16 double / quadruple the apply blocks and delay the
+// fused draw, 34 -> 42 / 50 us)
 constexpr int kApplyDetectWaves = CF_APPLY_DETECT_WAVES;
-#ifndef CF_APPLY_CHUNK
-// work items per detecting wave (<= 64).  A/B at cfg2: 64 best; 32 and 16
-// double / quadruple the apply blocks and delay the fused draw (34 -> 42 / 50
-// us); one-wave apply blocks (CF_APPLY_WAVE_BLOCKS) serialise ~3 owners per
-// group (standalone apply 24 -> 45 us)
-#define CF_APPLY_CHUNK 64
-#endif
 constexpr int kApplyChunk = CF_APPLY_CHUNK;
 
-// BS = workgroup size (256, or 64 for one-wave apply blocks)
-template <int EPL, int BS = kBlock, bool HOT = false>
+template <int EPL, bool HOT = false>
 __device__ __forceinline__ void apply_body(const ApplyArgs& a, int block, int nblocks) {
-    constexpr int NWV = BS / kWave, NGR = BS / kGL;
+    constexpr int BS = kBlock, NWV = BS / kWave, NGR = BS / kGL;
     const int lane = lane_id();
     const int wv = threadIdx.x >> 6;
     const int gl = lane & (kGL - 1);
@@ -3328,43 +2806,18 @@ __device__ __forceinline__ void apply_body(const ApplyArgs& a, int block, int nb
 
 template <int EPL, bool HOT>
 __global__ __launch_bounds__(kBlock) void apply_kernel(ApplyArgs a) {
-    apply_body<EPL, kBlock, HOT>(a, blockIdx.x, gridDim.x);
-}
-
-// one-wave apply blocks: the detecting wave's own four groups apply its owners
-template <int EPL>
-__global__ __launch_bounds__(kWave) void apply_wave_kernel(ApplyArgs a) {
-    apply_body<EPL, kWave>(a, blockIdx.x, gridDim.x);
+    apply_body<EPL, HOT>(a, blockIdx.x, gridDim.x);
 }
 
 // horizontal fusion on the device-sampler path: apply of step s (blocks
 // [0, napply)) beside the draw + count of step s+1 (the rest) -- independent
 // work (other buffer set), one launch instead of two
 template <int EPL, int MODEL, bool HOT>
-#ifndef CF_APPLY_PREP_ORDER
-#define CF_APPLY_PREP_ORDER 0  // 0: apply blocks first, 1: draw blocks first, 2: interleaved
-#endif
 __global__ __launch_bounds__(kBlock) void apply_prep_kernel(ApplyArgs p, StepArgs a, int napply) {
-#if CF_APPLY_PREP_ORDER != 0
-    const int nprep = (int)gridDim.x - napply;
-#endif
-#if CF_APPLY_PREP_ORDER == 2
-    int idx;
-    if (minor_block(blockIdx.x, napply, nprep, idx))
-        prep_any<MODEL>(a, idx);
-    else
-        apply_body<EPL, kBlock, HOT>(p, idx, napply);
-#elif CF_APPLY_PREP_ORDER == 1
-    if ((int)blockIdx.x < nprep)
-        prep_any<MODEL>(a, blockIdx.x);
-    else
-        apply_body<EPL, kBlock, HOT>(p, blockIdx.x - nprep, napply);
-#else
     if ((int)blockIdx.x < napply)
-        apply_body<EPL, kBlock, HOT>(p, blockIdx.x, napply);
+        apply_body<EPL, HOT>(p, blockIdx.x, napply);
     else
         prep_any<MODEL>(a, blockIdx.x - napply);
-#endif
 }
 
 // ---------------------------------------------------------------------------
@@ -3446,35 +2899,19 @@ static int epl_for(int d) {
     return e <= 1 ? 1 : e <= 2 ? 2 : e <= 4 ? 4 : e <= 8 ? 8 : 16;
 }
 
-#ifndef CF_FAST_PAIRS_W1
-#define CF_FAST_PAIRS_W1 1  // cfg2 grad: P=1 44.2 us, P=2 49.8, P=3 55.6, P=4 61.9 (occupancy wins)
-#endif
-#ifndef CF_FAST_PAIRS_W5
-#define CF_FAST_PAIRS_W5 1
-#endif
 // GBPR at d <= 64 (EPL <= 4): two pairs per 16-lane group keep more rows of
 // the 10M-user / 1M-item tables in flight (cfg4 grad 164.9 -> 157.6 us); at
 // d = 128 the second pair's registers cost occupancy (cfg5 AMF 148 -> 253 us)
-#ifndef CF_FAST_PAIRS_GBPR_W5
-#define CF_FAST_PAIRS_GBPR_W5 2
-#endif
 
-#ifndef CF_GRAD_LDS
-#define CF_GRAD_LDS 1   // 0: auto never takes grad_lds_kernel (grad_path 3 still does)
-#endif
-
-#ifndef CF_GRAD_LDS_GBPR
-#define CF_GRAD_LDS_GBPR 1   // 0: auto keeps GBPR (cfg4) on the phased kernel (grad_path 3 still takes it)
-#endif
 // the LDS-staged W = 5 kernel (grad_lds_kernel): grad_path 3, or auto where
 // it applies -- BPR / AMF / CML at d = 128, GBPR (G = 1) at d = 64; one pair
 // per 16-lane group, 16 per block
 static bool lds_path(const StepArgs& a) {
     if (a.apr) return false;   // AMF apr: the generic kernel (apr_pair)
-    const bool want = a.grad_path == 3 || (a.grad_path == 0 && CF_GRAD_LDS);
+    const bool want = a.grad_path == 3 || a.grad_path == 0;
     if (!want || a.W != 5 || a.srec != nullptr) return false;
     if (a.model == BPR || a.model == AMF || a.model == CML) return a.d == 128;
-    if (a.model == GBPR) return a.d == 64 && a.G == 1 && (a.grad_path == 3 || CF_GRAD_LDS_GBPR);
+    if (a.model == GBPR) return a.d == 64 && a.G == 1;
     return false;
 }
 
@@ -3491,12 +2928,6 @@ static int fast_w(const StepArgs& a) {
                     !(a.grad_path == 0 && a.model == CML && a.W == 5);
     return ok && (a.W == 1 || a.W == 5) ? a.W : 0;
 }
-
-#ifndef CF_GRAD_WAVE_BLOCKS
-// 1: fast path without draw blocks in one-wave workgroups (measured no faster
-// at cfg2: 43.9 vs 44.2 us), 0: 256-lane workgroups
-#define CF_GRAD_WAVE_BLOCKS 0
-#endif
 
 static int prep_blocks(const StepArgs* nx) {
     if (!nx || nx->B <= 0) return 0;
@@ -3548,18 +2979,6 @@ static hipError_t launch_sort_e(const StepArgs& a, const StepArgs& n, int ng, in
 
 template <int MODEL, int WT, int P>
 static hipError_t launch_grad_fast(const StepArgs& a, const StepArgs* nx, hipStream_t s) {
-    if (CF_GRAD_WAVE_BLOCKS && prep_blocks(nx) == 0) {
-        // the grid must match grad_blocks(): P * 4 pairs per one-wave block
-        constexpr int gpb = kWave / kGL;
-        const dim3 grid((a.B + P * gpb - 1) / (P * gpb)), block(kWave);
-        switch (epl_for(a.d)) {
-            case 1: hipLaunchKernelGGL((grad_fast_wave_kernel<MODEL, 1, WT, P>), grid, block, 0, s, a); break;
-            case 2: hipLaunchKernelGGL((grad_fast_wave_kernel<MODEL, 2, WT, P>), grid, block, 0, s, a); break;
-            case 4: hipLaunchKernelGGL((grad_fast_wave_kernel<MODEL, 4, WT, P>), grid, block, 0, s, a); break;
-            default: hipLaunchKernelGGL((grad_fast_wave_kernel<MODEL, 8, WT, P>), grid, block, 0, s, a); break;
-        }
-        return hipGetLastError();
-    }
     // the grid must match grad_blocks(): P * kGroupsPerBlock pairs per block
     const int ng = (a.B + P * kGroupsPerBlock - 1) / (P * kGroupsPerBlock), np = prep_blocks(nx);
     const StepArgs n = nx ? *nx : a;
@@ -3568,7 +2987,7 @@ static hipError_t launch_grad_fast(const StepArgs& a, const StepArgs* nx, hipStr
         if (a.srec != nullptr) {   // pos_sort; with nx (pipeline 3) the next draw rides along
             const int sg = (a.B + CF_SORT_TILES * kPsortPPB - 1) / (CF_SORT_TILES * kPsortPPB);
             const dim3 sgrid(sg + np);
-            const bool full = CF_ASSUME_FULL_ROWS && a.d == kGL * epl_for(a.d);
+            const bool full = a.d == kGL * epl_for(a.d);
             if (np > 0)
                 return a.det_fx ? launch_sort_e<MODEL, WT, true, true>(a, n, sg, np, sgrid, full, s)
                                 : launch_sort_e<MODEL, WT, false, true>(a, n, sg, np, sgrid, full, s);
@@ -3585,7 +3004,7 @@ static hipError_t launch_grad_fast(const StepArgs& a, const StepArgs* nx, hipStr
             default: hipLaunchKernelGGL((grad_fast_kernel<MODEL, 8, WT, P, true>), grid, block, 0, s, a, n, ng, np); break;
         }
     } else {
-        const bool full = CF_ASSUME_FULL_FAST && a.d == kGL * epl_for(a.d);
+        const bool full = a.d == kGL * epl_for(a.d);
         switch (epl_for(a.d)) {
             case 1: hipLaunchKernelGGL((grad_fast_kernel<MODEL, 1, WT, P, false>), grid, block, 0, s, a, n, ng, 0); break;
             case 2: hipLaunchKernelGGL((grad_fast_kernel<MODEL, 2, WT, P, false>), grid, block, 0, s, a, n, ng, 0); break;

@@ -525,10 +525,10 @@ int cf_score_topk_ex(cf_engine* eng, const int32_t* host_users, int32_t n,
  *                1 = probe an open-addressed set of the (u, i) pairs (16 B
  *                per interaction, built when selected; ~1 sector per
  *                candidate), 0 = scan the user's sorted CSR row (default:
- *                8 candidates per scan; A/B at cfg2 within noise), 2 = the
- *                set probed by one lane per pair (measured slower, DESIGN).
- *                The same batches every way: each negative takes its first
- *                attempt outside Pos(u) in the same draw sequence.
+ *                8 candidates per scan; A/B at cfg2 within noise).  The
+ *                same batches either way: each negative takes its first
+ *                attempt outside Pos(u) in the same draw sequence (DESIGN
+ *                3.1; 8 lists the removed one-lane-per-pair form).
  *   "bias_slots" GBPR / CPLR item bias of a duplicated row: 1 = stored in a
  *                bias slot beside the row's gradient slot and summed by the
  *                apply, 0 = one float atomic per occurrence (default: at
@@ -564,12 +564,11 @@ int cf_score_topk_ex(cf_engine* eng, const int32_t* host_users, int32_t n,
  *                occurrence whose slot row psort zeroes.  Same batches, same
  *                sums up to fp32 order; 0 (default since round 5's sorted
  *                batches: 3 us faster at cfg2) = count after the scan.
- *   "pair_prefetch" 1 = the pos_sort gradient launch also fetches the next
- *                step's shuffled pair records for its draw (cf_train_steps);
- *                measured slower at cfg2 (its registers cost the gradient
- *                launch a wave per SIMD), so 0 (default), and the default
- *                build compiles it out: 1 then fails with CF_EINVAL (build
- *                with -DCF_PAIR_PREFETCH=1).
+ *   "pair_prefetch" accepted at 0 only (any other value is CF_EINVAL).  1
+ *                used to make the pos_sort gradient launch fetch the next
+ *                step's pair records for its draw; it measured slower at
+ *                cfg2 and was removed ("Alternatives measured and
+ *                removed").
  *   "pos_sort"   1 = the gradient launch visits the batch's pairs in
  *                positive-item order (a counting sort by the draw's positive
  *                counts, two short launches before it), so the pairs of one

@@ -308,8 +308,7 @@ def test_pos_set_draw_equals_row_scan(fold1, model, W, G):
     """cf_set_option("neg_check"): the Pos(u) set probe and the CSR row scan
     take the same attempt sequence, so they draw identical batches -- on
     ml-100k fold 1 and on a dense toy graph where most candidates are
-    rejected.  (neg_check 2, the one-lane-per-pair draw, exists only in a
-    -DCF_LANE_DRAW build; it passed the same check at r02.)"""
+    rejected."""
     from collaborativefilteringusingtensorflow_amd.engine import Engine
     rng = np.random.RandomState(5)
     dense = []
@@ -337,6 +336,45 @@ def test_pos_set_draw_equals_row_scan(fold1, model, W, G):
             pairs, negs = ba[0], ba[1]
             for (u, i), js in zip(pairs, negs):
                 assert not any(int(j) in pos[u] for j in js)
+
+
+def test_removed_draw_options_keep_their_return_codes():
+    """The options of two removed draw variants keep their observable
+    behaviour: "pair_prefetch" is accepted at 0 only, "neg_check" at 0 and 1
+    only (CF_EINVAL = -1 otherwise), and setting pair_prefetch 0 changes no
+    batch."""
+    import ctypes
+    from collaborativefilteringusingtensorflow_amd import _native as N
+    from collaborativefilteringusingtensorflow_amd.engine import Engine
+    rng = np.random.RandomState(5)
+    rows = [np.sort(rng.choice(40, size=rng.randint(5, 39), replace=False)).astype(np.int32) for _ in range(30)]
+    ip = np.concatenate([[0], np.cumsum([len(r) for r in rows])]).astype(np.int64)
+    ix = np.concatenate(rows)
+    CF_OK, CF_EINVAL = 0, -1
+    assert N.STATUS[CF_EINVAL] == "CF_EINVAL"
+
+    def make():
+        e = Engine("bpr", 30, 40, 8, n_neg=1, seed=11)
+        e.set_interactions(ip, ix)
+        return e
+
+    def opt(e, name, value):
+        return e._L.cf_set_option(e._h, name.encode(), ctypes.c_int64(value))
+
+    plain, e = make(), make()
+    try:
+        assert opt(e, "pair_prefetch", 1) == CF_EINVAL
+        assert opt(e, "pair_prefetch", 2) == CF_EINVAL
+        assert opt(e, "pair_prefetch", -1) == CF_EINVAL
+        assert opt(e, "neg_check", 2) == CF_EINVAL
+        assert opt(e, "neg_check", 1) == CF_OK
+        assert opt(e, "neg_check", 0) == CF_OK
+        assert opt(e, "pair_prefetch", 0) == CF_OK
+        for xa, xb in zip(e.sample(64), plain.sample(64)):
+            assert np.array_equal(xa, xb)
+    finally:
+        e.close()
+        plain.close()
 
 
 def test_user_with_every_item_only_blocks_the_device_sampler():

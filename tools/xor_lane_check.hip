@@ -1,5 +1,5 @@
 // Checks on the GPU that cf_eval.hip's xor_lane (DPP / permlane-swap lane
-// exchange, CF_FUSED_DPP_SORT) returns lane ^ s's value for s = 1 .. 32:
+// exchange of the compaction sort) returns lane ^ s's value for s = 1 .. 32:
 //   hipcc -O3 --offload-arch=gfx950 tools/xor_lane_check.hip -o /tmp/xlc && /tmp/xlc
 #include <hip/hip_runtime.h>
 #include <cstdio>
