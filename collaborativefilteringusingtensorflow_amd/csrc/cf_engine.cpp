@@ -380,7 +380,7 @@ int items_per_pair(const cf_config& c) { return 1 + c.n_neg; }
 int group_count(const cf_config& c) { return c.model == CF_GBPR ? c.gsize : 0; }
 
 // pos_sort applies: BPR / AMF / CML steps on the phased gradient kernel
-// (must agree with fast_w() in cf_kernels.hip) and none of the modes it does
+// (must agree with grad_plan() in cf_kernels.hip) and none of the modes it does
 // not combine with
 // auto pos_sort from this batch size up: below it the sort launches cost more
 // than the fewer duplicate rows save (cfg2 A/B: -7 % at 2^19, -3.5 % at 2^18,
@@ -1092,7 +1092,8 @@ int begin_step(cf_engine* e, int B, const int32_t* pairs, const int32_t* negs,
 // Adagrad), duplicate apply (+ CML clip).  With `next`, the apply launch also
 // draws and counts the next step's batch (launch_apply_prep).  Loss added to
 // *loss_acc.
-ApplyArgs apply_args(cf_engine* e, const StepArgs& a, int B, int k, double* loss_acc) {
+ApplyArgs apply_args(cf_engine* e, const StepArgs& a, int B, int k, double* loss_acc,
+                     const StepArgs* grad_next = nullptr) {
     const cf_config& c = e->cfg;
     ApplyArgs p{};
     p.det_fx = a.det_fx;
@@ -1163,7 +1164,7 @@ ApplyArgs apply_args(cf_engine* e, const StepArgs& a, int B, int k, double* loss
     p.b = a.train_bias ? e->b : nullptr;  // PRIGP keeps b fixed (prigp.py:145)
     p.Ab = e->Ab; p.Gb = e->Gb;
     p.loss_partial = e->loss_partial;
-    p.n_partial = grad_blocks(a);
+    p.n_partial = grad_plan(a, grad_next).blocks;
     p.loss_acc = loss_acc;
     return p;
 }
@@ -1246,8 +1247,13 @@ int finish_step(cf_engine* e, const StepArgs& a, int B, int k, double* loss_acc,
                 const StepArgs* next) {
     CF_TRY(det_ranks(e, a));
     CF_TRY(psort(e, a));
-    ApplyArgs p = apply_args(e, a, B, k, loss_acc);
-    if (next && e->pipeline == 3 && a.srec != nullptr) {
+    // the draw of step s+1 rides in the gradient launch of step s (pipeline 2;
+    // pipeline 3 on pos_sort steps): the plan, and with it the loss partials
+    // the apply folds, is the one of that launch
+    const bool p3 = next && e->pipeline == 3 && a.srec != nullptr;
+    const bool p2 = next && e->pipeline == 2;
+    ApplyArgs p = apply_args(e, a, B, k, loss_acc, p3 || p2 ? next : nullptr);
+    if (p3) {
         // pipeline 3 (pos_sort steps): the draw + count of step s+1 rides in
         // the positive-sorted gradient launch of step s, the apply runs alone;
         // psort of s+1 follows the apply, so offPN / srec / slotN stay single
@@ -1260,8 +1266,7 @@ int finish_step(cf_engine* e, const StepArgs& a, int B, int k, double* loss_acc,
         if (e->prep_side) CF_HIP(hipEventRecord(e->bs[k].apply_done, e->stream));
         return pending_clips(e);
     }
-    if (next && e->pipeline == 2) {
-        p.n_partial = grad_blocks(a, true);   // the launch with draw blocks keeps 256-lane groups
+    if (p2) {
         // the draw + count of step s+1 rides in the gradient launch of step s
         // (other buffer set), the duplicate apply runs alone
         {
@@ -2633,7 +2638,7 @@ int cf_xchg_grad_part(cf_engine* e, int32_t part) {
     if (part != e->x_part + 1) return fail(CF_ESTATE, "gradient parts run in order: 1 (local members), then 2");
     StepArgs a = e->xb.args;
     a.member_pass = part;
-    if (part == 2) a.loss_partial = e->loss_partial + grad_blocks(e->xb.args);
+    if (part == 2) a.loss_partial = e->loss_partial + grad_plan(e->xb.args, nullptr).blocks;
     {
         ProfScope ps(e, part == 1 ? CF_K_STEP : CF_K_STEP_REMOTE);
         CF_HIP(launch_grad(a, e->stream));
@@ -2648,7 +2653,9 @@ int cf_xchg_grad_part(cf_engine* e, int32_t part) {
 }
 
 // loss partials of this exchange step's gradient launch(es)
-static int xchg_partials(cf_engine* e) { return grad_blocks(e->xb.args) * (e->x_part == 2 ? 2 : 1); }
+static int xchg_partials(cf_engine* e) {
+    return grad_plan(e->xb.args, nullptr).blocks * (e->x_part == 2 ? 2 : 1);
+}
 
 // split step: the item rows' summed gradient into the bound buffer (the item
 // exchange can start), before the served gradients arrive for the users
@@ -2990,10 +2997,13 @@ int cf_step_path(cf_engine* e, int32_t B, int32_t* flags_out) {
     a.W = c.n_neg;
     a.G = group_count(c);
     a.grad_path = e->grad_path;
+    a.apr = (c.model == CF_AMF && e->phase == 1 && c.amf_mode == CF_AMF_APR) ? 1 : 0;   // as base_step_args
+    a.B = B;
+    const int kind = grad_plan(a, nullptr).kind;
     int f = 0;
-    if (grad_fast_w(a) != 0) f |= CF_PATH_PHASED;
+    if (kind == kGradPhased || kind == kGradLds) f |= CF_PATH_PHASED;   // LDS-staged: a phased kernel too
     if (psort_active(e, B)) f |= CF_PATH_POS_SORT;
-    else if (grad_lds(a)) f |= CF_PATH_LDS;   // (pos_sort takes the sorted kernel)
+    else if (kind == kGradLds) f |= CF_PATH_LDS;   // (pos_sort takes the sorted kernel)
     if (e->item_recs && (!c.dense_item_apply || e->item_reduce)) f |= CF_PATH_ITEM_RECORDS;
     if (e->det) f |= CF_PATH_DETERMINISTIC;
     if (c.dense_item_apply) f |= CF_PATH_DENSE_ITEMS;

@@ -108,8 +108,8 @@ __global__ __launch_bounds__(kBlock) void apr_zero_kernel(StepArgs a, int64_t nU
 }
 
 // AMF apr, the gradient launch: grad_kernel's pair loop and loss partials
-// (one 16-lane group per pair, kPairsPerBlock pairs per block = grad_blocks()
-// of a generic step) with apr_pair's arithmetic; its own kernel so that the
+// (one 16-lane group per pair, kPairsPerBlock pairs per block: the kGradApr
+// plan is the generic step's) with apr_pair's arithmetic; its own kernel so that the
 // generic AMF kernel keeps its registers.  DRAW: pipeline 2's draw blocks.
 template <int EPL, int WT, bool DRAW>
 __global__ __launch_bounds__(kBlock) void apr_grad_kernel(StepArgs a, StepArgs nx, int ng, int np) {
@@ -150,50 +150,35 @@ __global__ __launch_bounds__(kBlock) void apr_grad_kernel(StepArgs a, StepArgs n
     }
 }
 
-template <int WT, bool DRAW>
-static hipError_t launch_apr_grad_w(const StepArgs& a, const StepArgs& n, int ng, int np, hipStream_t s) {
-    const dim3 grid(ng + np), block(kBlock);
-    switch (epl_for(a.d)) {
-        case 1: hipLaunchKernelGGL((apr_grad_kernel<1, WT, DRAW>), grid, block, 0, s, a, n, ng, np); break;
-        case 2: hipLaunchKernelGGL((apr_grad_kernel<2, WT, DRAW>), grid, block, 0, s, a, n, ng, np); break;
-        case 4: hipLaunchKernelGGL((apr_grad_kernel<4, WT, DRAW>), grid, block, 0, s, a, n, ng, np); break;
-        case 8: hipLaunchKernelGGL((apr_grad_kernel<8, WT, DRAW>), grid, block, 0, s, a, n, ng, np); break;
-        default: hipLaunchKernelGGL((apr_grad_kernel<16, WT, DRAW>), grid, block, 0, s, a, n, ng, np); break;
-    }
-    return hipGetLastError();
-}
-
 template <int WT>
-static hipError_t launch_apr_grad(const StepArgs& a, const StepArgs* nx, hipStream_t s) {
-    const int ng = (a.B + kPairsPerBlock - 1) / kPairsPerBlock, np = prep_blocks(nx);
+static hipError_t launch_apr_grad(const StepArgs& a, const StepArgs* nx, const GradPlan& pl, hipStream_t s) {
+    const int ng = pl.blocks, np = pl.draw_blocks;
     const StepArgs n = nx ? *nx : a;
-    return np > 0 ? launch_apr_grad_w<WT, true>(a, n, ng, np, s) : launch_apr_grad_w<WT, false>(a, n, ng, 0, s);
+    const dim3 grid(ng + np), block(kBlock);
+    if (np > 0)
+        return with_epl(a.d, [&](auto e) {
+            hipLaunchKernelGGL((apr_grad_kernel<decltype(e)::value, WT, true>), grid, block, 0, s, a, n, ng, np);
+        });
+    return with_epl(a.d, [&](auto e) {
+        hipLaunchKernelGGL((apr_grad_kernel<decltype(e)::value, WT, false>), grid, block, 0, s, a, n, ng, 0);
+    });
 }
 
+// one 16-lane group per pair, as the gradient launch that follows
 template <int WT>
 static hipError_t launch_apr_embed_w(const StepArgs& a, hipStream_t s) {
     const dim3 grid((a.B + kPairsPerBlock - 1) / kPairsPerBlock), block(kBlock);
-    switch (epl_for(a.d)) {
-        case 1: hipLaunchKernelGGL((apr_embed_kernel<1, WT>), grid, block, 0, s, a); break;
-        case 2: hipLaunchKernelGGL((apr_embed_kernel<2, WT>), grid, block, 0, s, a); break;
-        case 4: hipLaunchKernelGGL((apr_embed_kernel<4, WT>), grid, block, 0, s, a); break;
-        case 8: hipLaunchKernelGGL((apr_embed_kernel<8, WT>), grid, block, 0, s, a); break;
-        default: hipLaunchKernelGGL((apr_embed_kernel<16, WT>), grid, block, 0, s, a); break;
-    }
-    return hipGetLastError();
+    return with_epl(a.d, [&](auto e) {
+        hipLaunchKernelGGL((apr_embed_kernel<decltype(e)::value, WT>), grid, block, 0, s, a);
+    });
 }
 
 static hipError_t launch_apr_zero(const StepArgs& a, hipStream_t s) {
     const int64_t nU = a.B, n = nU + (int64_t)a.B * (1 + a.W);
     const dim3 grid((unsigned)((n * kGL + kBlock - 1) / kBlock)), block(kBlock);
-    switch (epl_for(a.d)) {
-        case 1: hipLaunchKernelGGL((apr_zero_kernel<1>), grid, block, 0, s, a, nU, n); break;
-        case 2: hipLaunchKernelGGL((apr_zero_kernel<2>), grid, block, 0, s, a, nU, n); break;
-        case 4: hipLaunchKernelGGL((apr_zero_kernel<4>), grid, block, 0, s, a, nU, n); break;
-        case 8: hipLaunchKernelGGL((apr_zero_kernel<8>), grid, block, 0, s, a, nU, n); break;
-        default: hipLaunchKernelGGL((apr_zero_kernel<16>), grid, block, 0, s, a, nU, n); break;
-    }
-    return hipGetLastError();
+    return with_epl(a.d, [&](auto e) {
+        hipLaunchKernelGGL((apr_zero_kernel<decltype(e)::value>), grid, block, 0, s, a, nU, n);
+    });
 }
 
 hipError_t launch_apr_embed(const StepArgs& a, hipStream_t s) {
@@ -202,8 +187,8 @@ hipError_t launch_apr_embed(const StepArgs& a, hipStream_t s) {
     return a.W == 1 ? launch_apr_embed_w<1>(a, s) : a.W == 5 ? launch_apr_embed_w<5>(a, s) : launch_apr_embed_w<0>(a, s);
 }
 
-hipError_t launch_grad_amf(const StepArgs& a, const StepArgs* nx, hipStream_t s) {
-    if (!a.apr || a.B <= 0) return launch_grad_m<AMF>(a, nx, s);
+hipError_t launch_grad_amf(const StepArgs& a, const StepArgs* nx, const GradPlan& pl, hipStream_t s) {
+    if (pl.kind != kGradApr) return launch_grad_m<AMF>(a, nx, pl, s);
     // apr runs on slot rows with counted users: no pos_sort, item records or
     // deterministic compact slots; items counted too unless every item row
     // reads the all-reduced buffer (apr_global, the multi-rank item reduce)
@@ -212,8 +197,8 @@ hipError_t launch_grad_amf(const StepArgs& a, const StepArgs* nx, hipStream_t s)
         return hipErrorInvalidValue;
     hipError_t err = hipSuccess;
     if (!a.apr_embed_done && (err = launch_apr_embed(a, s)) != hipSuccess) return err;
-    err = a.W == 1 ? launch_apr_grad<1>(a, nx, s)
-        : (a.W == 5 && epl_for(a.d) <= 8) ? launch_apr_grad<5>(a, nx, s) : launch_apr_grad<0>(a, nx, s);
+    err = pl.wt == 1 ? launch_apr_grad<1>(a, nx, pl, s)
+        : pl.wt == 5 ? launch_apr_grad<5>(a, nx, pl, s) : launch_apr_grad<0>(a, nx, pl, s);
     if (err != hipSuccess) return err;
     if ((err = launch_apr_zero(a, s)) != hipSuccess) return err;
     if (a.apr_global)   // rows of every rank's batch are set after the all-reduce

@@ -4,8 +4,8 @@
 
 namespace cfk {
 
-hipError_t launch_grad_cml(const StepArgs& a, const StepArgs* nx, hipStream_t s) {
-    return launch_grad_m<CML>(a, nx, s);
+hipError_t launch_grad_cml(const StepArgs& a, const StepArgs* nx, const GradPlan& pl, hipStream_t s) {
+    return launch_grad_m<CML>(a, nx, pl, s);
 }
 
 }  // namespace cfk

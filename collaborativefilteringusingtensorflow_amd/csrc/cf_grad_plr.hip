@@ -4,6 +4,6 @@
 
 namespace cfk {
 
-hipError_t launch_grad_plr_t(const StepArgs& a, hipStream_t s) { return launch_grad_plr(a, s); }
+hipError_t launch_grad_plr_t(const StepArgs& a, const GradPlan& pl, hipStream_t s) { return launch_grad_plr(a, pl, s); }
 
 }  // namespace cfk

@@ -394,13 +394,27 @@ hipError_t launch_prep(const StepArgs& a, hipStream_t s);   // sample/load + cou
 hipError_t launch_grad(const StepArgs& a, hipStream_t s, const StepArgs* next = nullptr);
 // AMF apr: the embedding-loss pass alone (cf_step_local_apr_embed)
 hipError_t launch_apr_embed(const StepArgs& a, hipStream_t s);
-// the phased gradient kernel's compile-time W (1 or 5) a step takes, 0 = generic
-int grad_fast_w(const StepArgs& a);
-// the step takes grad_lds_kernel (LDS-staged negatives)
-bool grad_lds(const StepArgs& a);
-// blocks (= loss partials) of the grad launch for this step shape
-int grad_blocks(const StepArgs& a, bool with_draw = false);
-int grad_blocks_max(int B);  // upper bound over every grad variant
+// The gradient launch of one step, decided once: launch_grad launches what
+// grad_plan(a, next) says, and the engine takes the loss partials it folds
+// (ApplyArgs::n_partial) and the path it reports (cf_step_path) from the same
+// plan.  `next` is the argument launch_grad gets.
+enum GradKind {
+    kGradNone,      // no kernel takes this step (launch_grad: hipErrorInvalidValue)
+    kGradGeneric,   // grad_kernel
+    kGradPhased,    // grad_fast_kernel
+    kGradSorted,    // grad_sort_kernel (pos_sort)
+    kGradLds,       // grad_lds_kernel (LDS-staged negatives)
+    kGradApr        // apr_grad_kernel (AMF apr)
+};
+struct GradPlan {
+    int kind;              // GradKind
+    int wt;                // compile-time W of the kernel (0 = runtime W)
+    int pairs_per_block;
+    int blocks;            // gradient blocks = loss partials written
+    int draw_blocks;       // blocks of next's draw riding in the launch
+};
+GradPlan grad_plan(const StepArgs& a, const StepArgs* next);
+int grad_blocks_max(int B);  // upper bound of GradPlan::blocks, times two
 hipError_t launch_apply(const ApplyArgs& a, hipStream_t s);
 // apply of step s and prep of step s+1 in one launch (device-sampler pipeline)
 hipError_t launch_apply_prep(const ApplyArgs& p, const StepArgs& next, hipStream_t s);

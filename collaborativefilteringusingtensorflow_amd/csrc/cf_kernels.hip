@@ -173,24 +173,88 @@ __global__ __launch_bounds__(kBlock) void xchg_accumulate_kernel(const int32_t* 
     gatomic<EPL>(GU, (int64_t)ids[j] - u0, d, gl, g);
 }
 
-int grad_fast_w(const StepArgs& a) { return fast_w(a); }
-bool grad_lds(const StepArgs& a) { return lds_path(a); }
-
-int grad_blocks(const StepArgs& a, bool with_draw) {
-    if (!with_draw && lds_path(a)) return (a.B + kGroupsPerBlock - 1) / kGroupsPerBlock;
-    if (a.srec != nullptr)   // grad_sort_kernel: CF_SORT_TILES tiles of kPsortPPB positions per block
-        return (a.B + CF_SORT_TILES * kPsortPPB - 1) / (CF_SORT_TILES * kPsortPPB);
-    const int fw = fast_w(a);
-    const int B = a.B;
-    const int p5 = (a.model == GBPR && epl_for(a.d) <= 4) ? CF_FAST_PAIRS_GBPR_W5 : CF_FAST_PAIRS_W5;
-    const int ppb = fw == 1 ? CF_FAST_PAIRS_W1 * kGroupsPerBlock
-                  : fw == 5 ? p5 * kGroupsPerBlock : kPairsPerBlock;
-    return (B + ppb - 1) / ppb;
+// the LDS-staged W = 5 kernel (grad_lds_kernel): grad_path 3, or auto where
+// it applies -- BPR / AMF / CML at d = 128, GBPR (G = 1) at d = 64; one pair
+// per 16-lane group, 16 per block
+static bool lds_path(const StepArgs& a) {
+    if (a.apr) return false;   // AMF apr: the generic kernel (apr_pair)
+    const bool want = a.grad_path == 3 || a.grad_path == 0;
+    if (!want || a.W != 5 || a.srec != nullptr) return false;
+    if (a.model == BPR || a.model == AMF || a.model == CML) return a.d == 128;
+    if (a.model == GBPR) return a.d == 64 && a.G == 1;
+    return false;
 }
 
-// B / 4: the split exchange step (part 2) also keeps two passes' partials of
-// B / 16 blocks each side by side in loss_partial
-int grad_blocks_max(int B) { return (B + kWave / kGL - 1) / (kWave / kGL); }
+// W = 1 (BPRMF driver) and W = 5 (AMF / CML / GBPR drivers) with G <= 1 and
+// d <= 128 take a phased kernel: its compile-time W (5 also where the
+// LDS-staged kernel applies), 0 = the generic kernel
+static int fast_w(const StepArgs& a) {
+    if (a.apr) return 0;   // AMF apr: the generic kernel (apr_pair)
+    if (lds_path(a)) return 5;
+    // CML at W = 5 keeps five distance rows and the clip live per pair: the
+    // generic kernel measured faster than the phased one there (cfg3: 160 vs
+    // 184 us), so auto (grad_path 0) leaves it on the generic kernel unless
+    // the LDS-staged kernel applies; 2 forces the phased kernel
+    const bool ok = a.grad_path != 1 && epl_for(a.d) <= 8 && (a.model != GBPR || a.G == 1) &&
+                    !(a.grad_path == 0 && a.model == CML && a.W == 5);
+    return ok && (a.W == 1 || a.W == 5) ? a.W : 0;
+}
+
+static int prep_blocks(const StepArgs* nx) {
+    if (!nx || nx->B <= 0) return 0;
+    const int ppb = prep_pairs_per_block(*nx);
+    return (nx->B + ppb - 1) / ppb;
+}
+
+// the fewest pairs a gradient block of any plan takes: one per 16-lane group
+constexpr int kGradMinPairsPerBlock = kGroupsPerBlock;
+static_assert(CF_FAST_PAIRS_W1 >= 1 && CF_FAST_PAIRS_W5 >= 1 && CF_FAST_PAIRS_GBPR_W5 >= 1 &&
+                  CF_SORT_TILES * kPsortPPB >= kGradMinPairsPerBlock && kPairsPerBlock >= kGradMinPairsPerBlock,
+              "grad_blocks_max: every plan's pairs_per_block is at least kGradMinPairsPerBlock");
+
+GradPlan grad_plan(const StepArgs& a, const StepArgs* next) {
+    GradPlan p{};
+    p.draw_blocks = prep_blocks(next);
+    const int e = epl_for(a.d), fw = fast_w(a);
+    if (a.model == PLR) {   // tuple ranking: prefetched tuples of width 4 (CPLR) or 5 (PRIGP)
+        p.kind = (a.W == 2 || a.W == 3) && a.srec == nullptr ? kGradGeneric : kGradNone;
+        p.wt = a.W;
+        p.pairs_per_block = kPairsPerBlock;
+    } else if (a.srec != nullptr) {
+        // pos_sort: grad_sort_kernel, CF_SORT_TILES tiles of kPsortPPB positions
+        // per block, for the steps a phased kernel with one pair per group takes
+        const bool one = (fw == 1 && CF_FAST_PAIRS_W1 == 1) || (fw == 5 && CF_FAST_PAIRS_W5 == 1);
+        p.kind = one && a.model != GBPR ? kGradSorted : kGradNone;
+        p.wt = fw;
+        p.pairs_per_block = CF_SORT_TILES * kPsortPPB;
+    } else if (lds_path(a) && p.draw_blocks == 0) {
+        // (with a fused draw, pipeline 2, such a step takes the phased kernel)
+        p.kind = kGradLds;
+        p.wt = 5;
+        p.pairs_per_block = kGroupsPerBlock;
+    } else if (fw != 0) {
+        // GBPR at d <= 64 (EPL <= 4): two pairs per 16-lane group keep more rows of
+        // the 10M-user / 1M-item tables in flight (cfg4 grad 164.9 -> 157.6 us); at
+        // d = 128 the second pair's registers cost occupancy (cfg5 AMF 148 -> 253 us)
+        const int P = fw == 1 ? CF_FAST_PAIRS_W1
+                    : (a.model == GBPR && e <= 4) ? CF_FAST_PAIRS_GBPR_W5 : CF_FAST_PAIRS_W5;
+        p.kind = kGradPhased;
+        p.wt = fw;
+        p.pairs_per_block = P * kGroupsPerBlock;
+    } else {
+        // grad_kernel, or with apr (AMF only) apr_grad_kernel: one pair per
+        // group at a time, kPairsPerGroup in turn
+        p.kind = a.apr && a.model == AMF ? kGradApr : kGradGeneric;
+        p.wt = a.W == 1 ? 1 : (a.W == 5 && e <= 8) ? 5 : 0;
+        p.pairs_per_block = kPairsPerBlock;
+    }
+    p.blocks = (a.B + p.pairs_per_block - 1) / p.pairs_per_block;
+    return p;
+}
+
+// sizes loss_partial for every plan: the split exchange step (part 2) keeps
+// two passes' partials side by side, each at most B / kGradMinPairsPerBlock
+int grad_blocks_max(int B) { return 2 * ((B + kGradMinPairsPerBlock - 1) / kGradMinPairsPerBlock); }
 
 hipError_t launch_prep(const StepArgs& a, hipStream_t s) {
     if (a.B <= 0) return hipSuccess;
@@ -206,13 +270,14 @@ hipError_t launch_prep(const StepArgs& a, hipStream_t s) {
 hipError_t launch_grad(const StepArgs& a, hipStream_t s, const StepArgs* next) {
     if (a.B <= 0) return next ? launch_prep(*next, s) : hipSuccess;
     if (next && next->model != a.model) return hipErrorInvalidValue;
-    if (a.srec != nullptr && fast_w(a) == 0) return hipErrorInvalidValue;   // pos_sort: phased kernel only
+    const GradPlan pl = grad_plan(a, next);
+    if (pl.kind == kGradNone) return hipErrorInvalidValue;   // e.g. pos_sort outside the phased kernels
     switch (a.model) {
-        case BPR: return launch_grad_bpr(a, next, s);
-        case GBPR: return launch_grad_gbpr(a, next, s);
-        case CML: return launch_grad_cml(a, next, s);
-        case PLR: return next ? hipErrorInvalidValue : launch_grad_plr_t(a, s);
-        default: return launch_grad_amf(a, next, s);
+        case BPR: return launch_grad_bpr(a, next, pl, s);
+        case GBPR: return launch_grad_gbpr(a, next, pl, s);
+        case CML: return launch_grad_cml(a, next, pl, s);
+        case PLR: return next ? hipErrorInvalidValue : launch_grad_plr_t(a, pl, s);
+        default: return launch_grad_amf(a, next, pl, s);
     }
 }
 
@@ -230,14 +295,9 @@ static int apply_grid(const ApplyArgs& a) {
 template <bool HOT>
 static hipError_t launch_apply_h(const ApplyArgs& a, hipStream_t s) {
     const dim3 grid(apply_grid(a)), block(kBlock);
-    switch (epl_for(a.d)) {
-        case 1: hipLaunchKernelGGL((apply_kernel<1, HOT>), grid, block, 0, s, a); break;
-        case 2: hipLaunchKernelGGL((apply_kernel<2, HOT>), grid, block, 0, s, a); break;
-        case 4: hipLaunchKernelGGL((apply_kernel<4, HOT>), grid, block, 0, s, a); break;
-        case 8: hipLaunchKernelGGL((apply_kernel<8, HOT>), grid, block, 0, s, a); break;
-        default: hipLaunchKernelGGL((apply_kernel<16, HOT>), grid, block, 0, s, a); break;
-    }
-    return hipGetLastError();
+    return with_epl(a.d, [&](auto e) {
+        hipLaunchKernelGGL((apply_kernel<decltype(e)::value, HOT>), grid, block, 0, s, a);
+    });
 }
 
 // the pos_sort apply (+ the next step's draw when nx is given); PS false: the
@@ -255,22 +315,13 @@ static hipError_t launch_apply_ps_t(const ApplyArgs& p, const StepArgs* nx, hipS
     const int nbI = (int)nbI64, nbW = (int)std::max<int64_t>(nbW64, nbI64 == 0 ? 1 : 0);   // block 0 folds the loss
     const dim3 grid(nbI + nbW + np), block(kBlock);
     const StepArgs n = nx ? *nx : StepArgs{};
-    if (np > 0) {
-        switch (epl_for(p.d)) {
-            case 1: hipLaunchKernelGGL((apply_ps_kernel<1, true, PS, FX>), grid, block, 0, s, p, n, nbI, nbW); break;
-            case 2: hipLaunchKernelGGL((apply_ps_kernel<2, true, PS, FX>), grid, block, 0, s, p, n, nbI, nbW); break;
-            case 4: hipLaunchKernelGGL((apply_ps_kernel<4, true, PS, FX>), grid, block, 0, s, p, n, nbI, nbW); break;
-            default: hipLaunchKernelGGL((apply_ps_kernel<8, true, PS, FX>), grid, block, 0, s, p, n, nbI, nbW); break;
-        }
-    } else {
-        switch (epl_for(p.d)) {
-            case 1: hipLaunchKernelGGL((apply_ps_kernel<1, false, PS, FX>), grid, block, 0, s, p, n, nbI, nbW); break;
-            case 2: hipLaunchKernelGGL((apply_ps_kernel<2, false, PS, FX>), grid, block, 0, s, p, n, nbI, nbW); break;
-            case 4: hipLaunchKernelGGL((apply_ps_kernel<4, false, PS, FX>), grid, block, 0, s, p, n, nbI, nbW); break;
-            default: hipLaunchKernelGGL((apply_ps_kernel<8, false, PS, FX>), grid, block, 0, s, p, n, nbI, nbW); break;
-        }
-    }
-    return hipGetLastError();
+    if (np > 0)
+        return with_epl<8>(p.d, [&](auto e) {
+            hipLaunchKernelGGL((apply_ps_kernel<decltype(e)::value, true, PS, FX>), grid, block, 0, s, p, n, nbI, nbW);
+        });
+    return with_epl<8>(p.d, [&](auto e) {
+        hipLaunchKernelGGL((apply_ps_kernel<decltype(e)::value, false, PS, FX>), grid, block, 0, s, p, n, nbI, nbW);
+    });
 }
 
 template <bool PS = true>
@@ -303,14 +354,9 @@ static hipError_t launch_apply_prep_m(const ApplyArgs& p, const StepArgs& a, hip
     const int na = apply_grid(p);
     const int np = prep_blocks(&a);
     const dim3 grid(na + np), block(kBlock);
-    switch (epl_for(p.d)) {
-        case 1: hipLaunchKernelGGL((apply_prep_kernel<1, MODEL, HOT>), grid, block, 0, s, p, a, na); break;
-        case 2: hipLaunchKernelGGL((apply_prep_kernel<2, MODEL, HOT>), grid, block, 0, s, p, a, na); break;
-        case 4: hipLaunchKernelGGL((apply_prep_kernel<4, MODEL, HOT>), grid, block, 0, s, p, a, na); break;
-        case 8: hipLaunchKernelGGL((apply_prep_kernel<8, MODEL, HOT>), grid, block, 0, s, p, a, na); break;
-        default: hipLaunchKernelGGL((apply_prep_kernel<16, MODEL, HOT>), grid, block, 0, s, p, a, na); break;
-    }
-    return hipGetLastError();
+    return with_epl(p.d, [&](auto e) {
+        hipLaunchKernelGGL((apply_prep_kernel<decltype(e)::value, MODEL, HOT>), grid, block, 0, s, p, a, na);
+    });
 }
 
 hipError_t launch_apply_prep(const ApplyArgs& p, const StepArgs& a, hipStream_t s) {
@@ -333,39 +379,24 @@ static int row_grid(int64_t n_rows) {
 
 hipError_t launch_apply_dense(const DenseArgs& a, hipStream_t s) {
     const dim3 grid(row_grid(a.n_rows)), block(kBlock);
-    switch (epl_for(a.d)) {
-        case 1: hipLaunchKernelGGL(apply_dense_kernel<1>, grid, block, 0, s, a); break;
-        case 2: hipLaunchKernelGGL(apply_dense_kernel<2>, grid, block, 0, s, a); break;
-        case 4: hipLaunchKernelGGL(apply_dense_kernel<4>, grid, block, 0, s, a); break;
-        case 8: hipLaunchKernelGGL(apply_dense_kernel<8>, grid, block, 0, s, a); break;
-        default: hipLaunchKernelGGL(apply_dense_kernel<16>, grid, block, 0, s, a); break;
-    }
-    return hipGetLastError();
+    return with_epl(a.d, [&](auto e) {
+        hipLaunchKernelGGL(apply_dense_kernel<decltype(e)::value>, grid, block, 0, s, a);
+    });
 }
 
 hipError_t launch_zero_rows(const int32_t* occ, int64_t n, float* G, float* Gb, int d, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     const dim3 grid(row_grid(n)), block(kBlock);
-    switch (epl_for(d)) {
-        case 1: hipLaunchKernelGGL(zero_rows_kernel<1>, grid, block, 0, s, occ, n, G, Gb, d); break;
-        case 2: hipLaunchKernelGGL(zero_rows_kernel<2>, grid, block, 0, s, occ, n, G, Gb, d); break;
-        case 4: hipLaunchKernelGGL(zero_rows_kernel<4>, grid, block, 0, s, occ, n, G, Gb, d); break;
-        case 8: hipLaunchKernelGGL(zero_rows_kernel<8>, grid, block, 0, s, occ, n, G, Gb, d); break;
-        default: hipLaunchKernelGGL(zero_rows_kernel<16>, grid, block, 0, s, occ, n, G, Gb, d); break;
-    }
-    return hipGetLastError();
+    return with_epl(d, [&](auto e) {
+        hipLaunchKernelGGL(zero_rows_kernel<decltype(e)::value>, grid, block, 0, s, occ, n, G, Gb, d);
+    });
 }
 
 hipError_t launch_clip_full(float* X, int64_t n_rows, int d, float c, hipStream_t s) {
     const dim3 grid(row_grid(n_rows)), block(kBlock);
-    switch (epl_for(d)) {
-        case 1: hipLaunchKernelGGL(clip_full_kernel<1>, grid, block, 0, s, X, n_rows, d, c); break;
-        case 2: hipLaunchKernelGGL(clip_full_kernel<2>, grid, block, 0, s, X, n_rows, d, c); break;
-        case 4: hipLaunchKernelGGL(clip_full_kernel<4>, grid, block, 0, s, X, n_rows, d, c); break;
-        case 8: hipLaunchKernelGGL(clip_full_kernel<8>, grid, block, 0, s, X, n_rows, d, c); break;
-        default: hipLaunchKernelGGL(clip_full_kernel<16>, grid, block, 0, s, X, n_rows, d, c); break;
-    }
-    return hipGetLastError();
+    return with_epl(d, [&](auto e) {
+        hipLaunchKernelGGL(clip_full_kernel<decltype(e)::value>, grid, block, 0, s, X, n_rows, d, c);
+    });
 }
 
 static int grid_for(int64_t n) {
@@ -420,28 +451,18 @@ hipError_t launch_xchg_serve(const int32_t* ids, int64_t n, int64_t u0, int32_t*
                              const float* U, float* rows, int d, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     const dim3 grid((unsigned)((n + kGroupsPerBlock - 1) / kGroupsPerBlock)), block(kBlock);
-    switch (epl_for(d)) {
-        case 1: hipLaunchKernelGGL(xchg_serve_kernel<1>, grid, block, 0, s, ids, n, u0, cntU, own, U, rows, d); break;
-        case 2: hipLaunchKernelGGL(xchg_serve_kernel<2>, grid, block, 0, s, ids, n, u0, cntU, own, U, rows, d); break;
-        case 4: hipLaunchKernelGGL(xchg_serve_kernel<4>, grid, block, 0, s, ids, n, u0, cntU, own, U, rows, d); break;
-        case 8: hipLaunchKernelGGL(xchg_serve_kernel<8>, grid, block, 0, s, ids, n, u0, cntU, own, U, rows, d); break;
-        default: hipLaunchKernelGGL(xchg_serve_kernel<16>, grid, block, 0, s, ids, n, u0, cntU, own, U, rows, d); break;
-    }
-    return hipGetLastError();
+    return with_epl(d, [&](auto e) {
+        hipLaunchKernelGGL(xchg_serve_kernel<decltype(e)::value>, grid, block, 0, s, ids, n, u0, cntU, own, U, rows, d);
+    });
 }
 
 hipError_t launch_xchg_accumulate(const int32_t* ids, int64_t n, int64_t u0, const float* grads,
                                   float* GU, int d, hipStream_t s) {
     if (n <= 0) return hipSuccess;
     const dim3 grid((unsigned)((n + kGroupsPerBlock - 1) / kGroupsPerBlock)), block(kBlock);
-    switch (epl_for(d)) {
-        case 1: hipLaunchKernelGGL(xchg_accumulate_kernel<1>, grid, block, 0, s, ids, n, u0, grads, GU, d); break;
-        case 2: hipLaunchKernelGGL(xchg_accumulate_kernel<2>, grid, block, 0, s, ids, n, u0, grads, GU, d); break;
-        case 4: hipLaunchKernelGGL(xchg_accumulate_kernel<4>, grid, block, 0, s, ids, n, u0, grads, GU, d); break;
-        case 8: hipLaunchKernelGGL(xchg_accumulate_kernel<8>, grid, block, 0, s, ids, n, u0, grads, GU, d); break;
-        default: hipLaunchKernelGGL(xchg_accumulate_kernel<16>, grid, block, 0, s, ids, n, u0, grads, GU, d); break;
-    }
-    return hipGetLastError();
+    return with_epl(d, [&](auto e) {
+        hipLaunchKernelGGL(xchg_accumulate_kernel<decltype(e)::value>, grid, block, 0, s, ids, n, u0, grads, GU, d);
+    });
 }
 
 __global__ void uncount_kernel(const int32_t* __restrict__ occ, int64_t n, int32_t* __restrict__ cnt) {
@@ -534,14 +555,9 @@ hipError_t launch_det_hot(const HotArgs& h, hipStream_t s) {
     const int64_t ntiles = h.n / kDetTile;
     if (ntiles <= 0) return hipSuccess;
     const dim3 grid((unsigned)(ntiles < 16384 ? ntiles : 16384)), block(kBlock);
-    switch (epl_for(h.d)) {
-        case 1: hipLaunchKernelGGL(det_hot_kernel<1>, grid, block, 0, s, h); break;
-        case 2: hipLaunchKernelGGL(det_hot_kernel<2>, grid, block, 0, s, h); break;
-        case 4: hipLaunchKernelGGL(det_hot_kernel<4>, grid, block, 0, s, h); break;
-        case 8: hipLaunchKernelGGL(det_hot_kernel<8>, grid, block, 0, s, h); break;
-        default: hipLaunchKernelGGL(det_hot_kernel<16>, grid, block, 0, s, h); break;
-    }
-    return hipGetLastError();
+    return with_epl(h.d, [&](auto e) {
+        hipLaunchKernelGGL(det_hot_kernel<decltype(e)::value>, grid, block, 0, s, h);
+    });
 }
 
 }  // namespace cfk

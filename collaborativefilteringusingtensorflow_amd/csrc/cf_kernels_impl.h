@@ -41,6 +41,7 @@
 // gbprmf.py:58-106, cml.py:55-129, src/models/others/models/amf.py:66-162;
 // samplers src/samplers/sampler_ranking.py:22-37, sampler_gbpr.py:23-43.
 #include <algorithm>
+#include <type_traits>
 
 #include "cf_kernels.h"
 #include "cf_device.h"
@@ -1209,12 +1210,27 @@ __device__ __forceinline__ void gload_acc(const float* __restrict__ A, int64_t r
     if (want) row_ld<EPL>(A + r * (int64_t)d, d, gl, 1.f, acc);
 }
 
-// SparseApplyAdagrad with the accumulator row already in registers
-template <int EPL>
-__device__ __forceinline__ void gapply_pre(float* __restrict__ X, float* __restrict__ A, int64_t r,
-                                           int d, int gl, const float (&x0)[EPL],
-                                           const float (&acc0)[EPL], const float (&g)[EPL],
-                                           float lr, bool clip, float c) {
+// How a 16-lane group holds a row: the element mapping of row_ld / row_st
+// (VecRows), or the LDS-staged kernel's parity mapping (ParRows, below)
+struct VecRows {
+    template <int EPL>
+    static __device__ __forceinline__ void st(float* __restrict__ row, int d, int gl, int, const float (&x)[EPL]) {
+        row_st<EPL>(row, d, gl, x);
+    }
+    template <int EPL>
+    static __device__ __forceinline__ void atomic(float* __restrict__ G, int64_t r, int d, int gl, int,
+                                                  const float (&g)[EPL]) {
+        gatomic<EPL>(G, r, d, gl, g);
+    }
+};
+
+// SparseApplyAdagrad (see gapply) with the accumulator row acc0 already in
+// registers; Layout stores the rows
+template <int EPL, class Layout>
+__device__ __forceinline__ void adagrad_row(float* __restrict__ X, float* __restrict__ A, int64_t r,
+                                            int d, int gl, int par, const float (&x0)[EPL],
+                                            const float (&acc0)[EPL], const float (&g)[EPL],
+                                            float lr, bool clip, float c) {
     float acc[EPL], x[EPL];
 #pragma unroll
     for (int s = 0; s < EPL; ++s) {
@@ -1227,46 +1243,48 @@ __device__ __forceinline__ void gapply_pre(float* __restrict__ X, float* __restr
 #pragma unroll
         for (int s = 0; s < EPL; ++s) x[s] = (x[s] * c) / den;
     }
-    row_st<EPL>(X + r * (int64_t)d, d, gl, x);
-    row_st<EPL>(A + r * (int64_t)d, d, gl, acc);
+    Layout::template st<EPL>(X + r * (int64_t)d, d, gl, par, x);
+    Layout::template st<EPL>(A + r * (int64_t)d, d, gl, par, acc);
 }
 
-template <int EPL>
-__device__ __forceinline__ void gfinish_pre(float* __restrict__ X, float* __restrict__ A,
-                                            float* __restrict__ G, float* __restrict__ S,
-                                            int32_t* __restrict__ cnt,
-                                            int64_t r, int count, int64_t slot, int d, int gl,
-                                            const float (&x0)[EPL], const float (&acc0)[EPL],
-                                            const float (&g)[EPL], const StepArgs& a) {
+// row r of X with its accumulator row in registers (see gfinish); FXU: with
+// the deterministic pos_sort arm of a user past its slot cap
+template <int EPL, class Layout, bool FXU>
+__device__ __forceinline__ void finish_row(float* __restrict__ X, float* __restrict__ A,
+                                           float* __restrict__ G, float* __restrict__ S,
+                                           int32_t* __restrict__ cnt,
+                                           int64_t r, int count, int64_t slot, int d, int gl, int par,
+                                           const float (&x0)[EPL], const float (&acc0)[EPL],
+                                           const float (&g)[EPL], const StepArgs& a) {
     if (count == 1) {
         if (a.items_grad_only && X == a.V) {
-            gstore<EPL>(G, r, d, gl, g);  // sole writer of the zeroed dense row
+            Layout::template st<EPL>(G + r * (int64_t)d, d, gl, par, g);  // sole writer of the zeroed dense row
         } else {
-            gapply_pre<EPL>(X, A, r, d, gl, x0, acc0, g, a.lr, a.clip != 0, a.clip_norm);
+            adagrad_row<EPL, Layout>(X, A, r, d, gl, par, x0, acc0, g, a.lr, a.clip != 0, a.clip_norm);
         }
         if (gl == 0) cnt[r] = 0;
     } else if (slot >= 0) {
-        gstore<EPL>(S, slot, d, gl, g);
+        Layout::template st<EPL>(S + slot * (int64_t)d, d, gl, par, g);
     } else {
-        if (a.GU64 != nullptr && X == a.U)   // deterministic pos_sort: a user past its slot cap
+        if (FXU && a.GU64 != nullptr && X == a.U)   // deterministic pos_sort: a user past its slot cap
             fx_atomic<EPL>(a.GU64 + (int64_t)a.hotU[r] * d, d, gl, g, a.fx_bad);
         else
-            gatomic<EPL>(acc_of(G, slot, a), r, d, gl, g);
+            Layout::template atomic<EPL>(acc_of(G, slot, a), r, d, gl, par, g);
         if (a.items_grad_only && a.capV == 0 && X == a.V && gl == 0) cnt[r] = 0;  // see gfinish
     }
 }
 
-// gfinish_pre with ifinish's item records (see there)
-template <int EPL>
-__device__ __forceinline__ void ifinish_pre(const StepArgs& a, int64_t r, int count, int64_t slot, int p,
-                                            float alpha, float beta, int which, int gl,
+// finish_row with ifinish's item records (see there)
+template <int EPL, class Layout, bool FXU>
+__device__ __forceinline__ void ifinish_row(const StepArgs& a, int64_t r, int count, int64_t slot, int p,
+                                            float alpha, float beta, int which, int gl, int par,
                                             const float (&x0)[EPL], const float (&acc0)[EPL],
                                             const float (&g)[EPL]) {
     if (a.recV != nullptr && count >= 2 && slot >= 0) {
         if (gl == 0) a.recV[slot] = make_int4(p, __float_as_int(alpha), __float_as_int(beta), which);
         return;
     }
-    gfinish_pre<EPL>(a.V, a.AV, a.GV, a.slotV, a.cntV, r, count, slot, a.d, gl, x0, acc0, g, a);
+    finish_row<EPL, Layout, FXU>(a.V, a.AV, a.GV, a.slotV, a.cntV, r, count, slot, a.d, gl, par, x0, acc0, g, a);
 }
 
 template <int MODEL, int EPL, int WT>
@@ -1432,7 +1450,7 @@ struct PairRows {
                     gj[s] = -c * uu[s] + a.reg * vj[w][s];
                     sq = fmaf(vj[w][s], vj[w][s], sq);
                 }
-                ifinish_pre<EPL>(a, j[w], cj[w], sj[w], p, -c, a.reg, 0, gl, vj[w], aj[w], gj);
+                ifinish_row<EPL, VecRows, true>(a, j[w], cj[w], sj[w], p, -c, a.reg, 0, gl, 0, vj[w], aj[w], gj);
             }
             float gi[EPL];
 #pragma unroll
@@ -1442,12 +1460,12 @@ struct PairRows {
                 sq = fmaf(uu[s], uu[s], sq);
                 sq = fmaf(vi[s], vi[s], sq);
             }
-            gfinish_pre<EPL>(a.U, a.AU, a.GU, a.slotU, a.cntU, u, cu, su, d, gl, uu, au, gu, a);
+            finish_row<EPL, VecRows, true>(a.U, a.AU, a.GU, a.slotU, a.cntU, u, cu, su, d, gl, 0, uu, au, gu, a);
             if constexpr (SORT) {
 #pragma unroll
                 for (int s = 0; s < EPL; ++s) srow[s * kGL + gl] = gi[s];
             } else {
-                ifinish_pre<EPL>(a, i, ci, si, p, sc, a.reg, 0, gl, vi, ai, gi);
+                ifinish_row<EPL, VecRows, true>(a, i, ci, si, p, sc, a.reg, 0, gl, 0, vi, ai, gi);
             }
         } else if (MODEL == GBPR) {  // G == 1
             const float ui_u = gdot<EPL>(uu, vi);
@@ -1471,7 +1489,7 @@ struct PairRows {
                     gj[s] = -c * uu[s];
                 }
                 if (gl == 0) bias_finish_pre(a, j[w], cj[w], -c + a.reg * bj[w], sj[w], bj[w], abj[w]);
-                ifinish_pre<EPL>(a, j[w], cj[w], sj[w], p, -c, 0.f, 0, gl, vj[w], aj[w], gj);
+                ifinish_row<EPL, VecRows, true>(a, j[w], cj[w], sj[w], p, -c, 0.f, 0, gl, 0, vj[w], aj[w], gj);
             }
             const float rg = a.rho;  // rho / G with G == 1
             float gi[EPL], gg[EPL], bl[EPL];
@@ -1484,14 +1502,15 @@ struct PairRows {
                 sq = fmaf(uu[s], uu[s], sq);
                 sq = fmaf(vi[s], vi[s], sq);
             }
-            gfinish_pre<EPL>(a.U, a.AU, a.GU, a.slotU, a.cntU, u, cu, su, d, gl, uu, au, gu, a);
+            finish_row<EPL, VecRows, true>(a.U, a.AU, a.GU, a.slotU, a.cntU, u, cu, su, d, gl, 0, uu, au, gu, a);
             if (g[0] >= 0)
-                gfinish_pre<EPL>(a.U, a.AU, a.GU, a.slotU, a.cntU, g[0], cg[0], sg[0], d, gl, ug[0], ag[0], gg, a);
+                finish_row<EPL, VecRows, true>(a.U, a.AU, a.GU, a.slotU, a.cntU, g[0], cg[0], sg[0], d, gl, 0, ug[0],
+                                               ag[0], gg, a);
             else  // another rank's user: its gradient row goes back to the owner
                 gstore<EPL>(a.xgrads, -1 - g[0], d, gl, gg);
             if (gl == 0) bias_finish_pre(a, i, ci, sc, si, bi, abi);
             if (a.recV != nullptr && ci >= 2 && si >= 0) gstore<EPL>(a.stashB, p, d, gl, bl);
-            ifinish_pre<EPL>(a, i, ci, si, p, sc, a.reg, 1, gl, vi, ai, gi);
+            ifinish_row<EPL, VecRows, true>(a, i, ci, si, p, sc, a.reg, 1, gl, 0, vi, ai, gi);
         } else {  // CML
             float du[EPL];
 #pragma unroll
@@ -1539,8 +1558,8 @@ struct PairRows {
                         sq = fmaf(vj[w][s], vj[w][s], sq);
                     }
                 }
-                ifinish_pre<EPL>(a, j[w], cj[w], sj[w], p, coef, (l2 ? a.reg_cov : 0.f) - coef, 0, gl,
-                                 vj[w], aj[w], gj);
+                ifinish_row<EPL, VecRows, true>(a, j[w], cj[w], sj[w], p, coef, (l2 ? a.reg_cov : 0.f) - coef, 0, gl, 0,
+                                                vj[w], aj[w], gj);
             }
             if (l2) {
 #pragma unroll
@@ -1551,12 +1570,13 @@ struct PairRows {
                     sq = fmaf(vi[s], vi[s], sq);
                 }
             }
-            gfinish_pre<EPL>(a.U, a.AU, a.GU, a.slotU, a.cntU, u, cu, su, d, gl, uu, au, gu, a);
+            finish_row<EPL, VecRows, true>(a.U, a.AU, a.GU, a.slotU, a.cntU, u, cu, su, d, gl, 0, uu, au, gu, a);
             if constexpr (SORT) {
 #pragma unroll
                 for (int s = 0; s < EPL; ++s) srow[s * kGL + gl] = gi[s];
             } else {
-                ifinish_pre<EPL>(a, i, ci, si, p, -2.f * aa, 2.f * aa + (l2 ? a.reg_cov : 0.f), 0, gl, vi, ai, gi);
+                ifinish_row<EPL, VecRows, true>(a, i, ci, si, p, -2.f * aa, 2.f * aa + (l2 ? a.reg_cov : 0.f), 0, gl,
+                                                0, vi, ai, gi);
             }
         }
     }
@@ -1605,7 +1625,7 @@ __device__ __forceinline__ void psort_head(const StepArgs& a, const PairRows<MOD
         if (a.items_grad_only)   // multi-rank item reduce: the sole writer of the zeroed dense row
             gstore<EPL>(a.GV, r.i, a.d, gl, g);
         else
-            gapply_pre<EPL>(a.V, a.AV, r.i, a.d, gl, r.vi, r.ai, g, a.lr, a.clip != 0, a.clip_norm);
+            adagrad_row<EPL, VecRows>(a.V, a.AV, r.i, a.d, gl, 0, r.vi, r.ai, g, a.lr, a.clip != 0, a.clip_norm);
         if (gl == 0) a.cntP[r.i] = 0;
     } else {
         if (k < a.capP)
@@ -1783,57 +1803,19 @@ __device__ __forceinline__ void prow_atomic(float* __restrict__ row, int gl, int
     for (int s = 0; s < EPL; ++s) unsafeAtomicAdd(row + elem_par(s, gl, par), g[s]);
 }
 
-// gapply_pre / gfinish_pre / ifinish_pre in the parity mapping
-template <int EPL>
-__device__ __forceinline__ void papply(float* __restrict__ X, float* __restrict__ A, int64_t r, int d, int gl,
-                                       int par, const float (&x0)[EPL], const float (&acc0)[EPL],
-                                       const float (&g)[EPL], float lr, bool clip, float c) {
-    float acc[EPL], x[EPL];
-#pragma unroll
-    for (int s = 0; s < EPL; ++s) {
-        acc[s] = fmaf(g[s], g[s], acc0[s]);
-        x[s] = x0[s] - adagrad_delta(lr, g[s], acc[s]);
+struct ParRows {
+    template <int EPL>
+    static __device__ __forceinline__ void st(float* __restrict__ row, int, int gl, int par, const float (&x)[EPL]) {
+        prow_st<EPL>(row, gl, par, x);
     }
-    if (clip) {
-        const float n = sqrtf(gdot<EPL>(x, x));
-        const float den = fmaxf(n, c);
-#pragma unroll
-        for (int s = 0; s < EPL; ++s) x[s] = (x[s] * c) / den;
+    template <int EPL>
+    static __device__ __forceinline__ void atomic(float* __restrict__ G, int64_t r, int d, int gl, int par,
+                                                  const float (&g)[EPL]) {
+        prow_atomic<EPL>(G + r * (int64_t)d, gl, par, g);
     }
-    prow_st<EPL>(X + r * (int64_t)d, gl, par, x);
-    prow_st<EPL>(A + r * (int64_t)d, gl, par, acc);
-}
+};
 
-template <int EPL>
-__device__ __forceinline__ void pfinish(float* __restrict__ X, float* __restrict__ A, float* __restrict__ G,
-                                        float* __restrict__ S, int32_t* __restrict__ cnt, int64_t r, int count,
-                                        int64_t slot, int d, int gl, int par, const float (&x0)[EPL],
-                                        const float (&acc0)[EPL], const float (&g)[EPL], const StepArgs& a) {
-    if (count == 1) {
-        if (a.items_grad_only && X == a.V)
-            prow_st<EPL>(G + r * (int64_t)d, gl, par, g);   // sole writer of the zeroed dense row
-        else
-            papply<EPL>(X, A, r, d, gl, par, x0, acc0, g, a.lr, a.clip != 0, a.clip_norm);
-        if (gl == 0) cnt[r] = 0;
-    } else if (slot >= 0) {
-        prow_st<EPL>(S + slot * (int64_t)d, gl, par, g);
-    } else {
-        prow_atomic<EPL>(acc_of(G, slot, a) + r * (int64_t)d, gl, par, g);
-        if (a.items_grad_only && a.capV == 0 && X == a.V && gl == 0) cnt[r] = 0;  // see gfinish
-    }
-}
-
-template <int EPL>
-__device__ __forceinline__ void pifinish(const StepArgs& a, int64_t r, int count, int64_t slot, int p,
-                                         float alpha, float beta, int which, int gl, int par,
-                                         const float (&x0)[EPL], const float (&acc0)[EPL],
-                                         const float (&g)[EPL]) {
-    if (a.recV != nullptr && count >= 2 && slot >= 0) {
-        if (gl == 0) a.recV[slot] = make_int4(p, __float_as_int(alpha), __float_as_int(beta), which);
-        return;
-    }
-    pfinish<EPL>(a.V, a.AV, a.GV, a.slotV, a.cntV, r, count, slot, a.d, gl, par, x0, acc0, g, a);
-}
+// (finish_row / ifinish_row take the parity mapping as ParRows)
 
 template <int EPL>
 __device__ __forceinline__ void pacc_ld(const float* __restrict__ A, int64_t r, int d, int gl, int par, bool want,
@@ -2032,8 +2014,8 @@ __global__ __launch_bounds__(kBlock) CF_LDS_ATTR void grad_lds_kernel(StepArgs a
                 sq = fmaf(uu[s], uu[s], sq);
                 sq = fmaf(vi[s], vi[s], sq);
             }
-            pfinish<EPL>(a.U, a.AU, a.GU, a.slotU, a.cntU, u, cu, su, d, gl, par, uu, au, gu, a);
-            pifinish<EPL>(a, i, ci, si, p, sc, a.reg, 0, gl, par, vi, ai, gi);
+            finish_row<EPL, ParRows, false>(a.U, a.AU, a.GU, a.slotU, a.cntU, u, cu, su, d, gl, par, uu, au, gu, a);
+            ifinish_row<EPL, ParRows, false>(a, i, ci, si, p, sc, a.reg, 0, gl, par, vi, ai, gi);
 #pragma unroll
             for (int w = 0; w < WT; ++w) {
                 __builtin_amdgcn_sched_barrier(0);
@@ -2042,7 +2024,7 @@ __global__ __launch_bounds__(kBlock) CF_LDS_ATTR void grad_lds_kernel(StepArgs a
                 prow_ld<EPL>(sv + w * ROW, gl, par, vj);
 #pragma unroll
                 for (int s = 0; s < EPL; ++s) gj[s] = -cw[w] * uu[s] + a.reg * vj[s];
-                pifinish<EPL>(a, j[w], cj[w], sj[w], p, -cw[w], a.reg, 0, gl, par, vj, aj, gj);
+                ifinish_row<EPL, ParRows, false>(a, j[w], cj[w], sj[w], p, -cw[w], a.reg, 0, gl, par, vj, aj, gj);
             }
         } else if (MODEL == CML) {
             float du[EPL];
@@ -2096,8 +2078,8 @@ __global__ __launch_bounds__(kBlock) CF_LDS_ATTR void grad_lds_kernel(StepArgs a
                     }
                 }
                 // a touched row with a zero gradient is still clipped (cml.py:128-129)
-                pifinish<EPL>(a, j[w], cj[w], sj[w], p, coef, (l2 ? a.reg_cov : 0.f) - coef, 0, gl, par, vj,
-                              aj, gj);
+                ifinish_row<EPL, ParRows, false>(a, j[w], cj[w], sj[w], p, coef, (l2 ? a.reg_cov : 0.f) - coef, 0,
+                                                 gl, par, vj, aj, gj);
             }
             if (l2) {
 #pragma unroll
@@ -2108,8 +2090,9 @@ __global__ __launch_bounds__(kBlock) CF_LDS_ATTR void grad_lds_kernel(StepArgs a
                     sq = fmaf(vi[s], vi[s], sq);
                 }
             }
-            pfinish<EPL>(a.U, a.AU, a.GU, a.slotU, a.cntU, u, cu, su, d, gl, par, uu, au, gu, a);
-            pifinish<EPL>(a, i, ci, si, p, -2.f * aa, 2.f * aa + (l2 ? a.reg_cov : 0.f), 0, gl, par, vi, ai, gi);
+            finish_row<EPL, ParRows, false>(a.U, a.AU, a.GU, a.slotU, a.cntU, u, cu, su, d, gl, par, uu, au, gu, a);
+            ifinish_row<EPL, ParRows, false>(a, i, ci, si, p, -2.f * aa, 2.f * aa + (l2 ? a.reg_cov : 0.f), 0, gl,
+                                             par, vi, ai, gi);
         } else if constexpr (MODEL == GBPR) {   // G == 1 (gbprmf.py:58-106)
 #pragma unroll
             for (int s = 0; s < EPL; ++s) sq = fmaf(ug[s], ug[s], sq);
@@ -2142,14 +2125,14 @@ __global__ __launch_bounds__(kBlock) CF_LDS_ATTR void grad_lds_kernel(StepArgs a
                 sq = fmaf(uu[s], uu[s], sq);
                 sq = fmaf(vi[s], vi[s], sq);
             }
-            pfinish<EPL>(a.U, a.AU, a.GU, a.slotU, a.cntU, u, cu, su, d, gl, par, uu, au, gu, a);
+            finish_row<EPL, ParRows, false>(a.U, a.AU, a.GU, a.slotU, a.cntU, u, cu, su, d, gl, par, uu, au, gu, a);
             if (g >= 0)
-                pfinish<EPL>(a.U, a.AU, a.GU, a.slotU, a.cntU, g, cg, sg, d, gl, par, ug, ag, gg, a);
+                finish_row<EPL, ParRows, false>(a.U, a.AU, a.GU, a.slotU, a.cntU, g, cg, sg, d, gl, par, ug, ag, gg, a);
             else   // another rank's user: its gradient row goes back to the owner
                 prow_st<EPL>(a.xgrads + (int64_t)(-1 - g) * d, gl, par, gg);
             if (gl == 0) bias_finish_pre(a, i, ci, sc, si, bi, abi);
             if (a.recV != nullptr && ci >= 2 && si >= 0) prow_st<EPL>(a.stashB + (int64_t)p * d, gl, par, bl);
-            pifinish<EPL>(a, i, ci, si, p, sc, a.reg, 1, gl, par, vi, ai, gi);
+            ifinish_row<EPL, ParRows, false>(a, i, ci, si, p, sc, a.reg, 1, gl, par, vi, ai, gi);
 #pragma unroll
             for (int w = 0; w < WT; ++w) {
                 __builtin_amdgcn_sched_barrier(0);
@@ -2158,7 +2141,8 @@ __global__ __launch_bounds__(kBlock) CF_LDS_ATTR void grad_lds_kernel(StepArgs a
 #pragma unroll
                 for (int s = 0; s < EPL; ++s) gj[s] = -cw[w] * uu[s];   // no L2 on V[j] (gbprmf.py:59-64)
                 if (gl == 0) bias_finish_pre(a, j[w], cj[w], -cw[w] + a.reg * bj[w], sj[w], bj[w], abj[w]);
-                pifinish<EPL>(a, j[w], cj[w], sj[w], p, -cw[w], 0.f, 0, gl, par, vj, aje[ACC_EARLY ? w : 0], gj);
+                ifinish_row<EPL, ParRows, false>(a, j[w], cj[w], sj[w], p, -cw[w], 0.f, 0, gl, par, vj,
+                                                 aje[ACC_EARLY ? w : 0], gj);
             }
         }
     }
@@ -2350,7 +2334,7 @@ __device__ __forceinline__ void apply_row(const ApplyArgs& a, int64_t r, bool is
         }
         return;
     }
-    gapply_pre<EPL>(X, A, r, a.d, gl, x, acc, g, a.lr, a.clip != 0, a.clip_norm);
+    adagrad_row<EPL, VecRows>(X, A, r, a.d, gl, 0, x, acc, g, a.lr, a.clip != 0, a.clip_norm);
     if (gl == 0) {
         cnt[r] = 0;
         if (!isU && a.b != nullptr) {
@@ -2481,7 +2465,7 @@ __device__ __forceinline__ void apply_item_ps(const ApplyArgs& a, int64_t r, int
     if (reduce_only)
         row_st<EPL>(a.GV + r * (int64_t)a.d, a.d, gl, g);
     else
-        gapply_pre<EPL>(a.V, a.AV, r, a.d, gl, x, acc, g, a.lr, a.clip != 0, a.clip_norm);
+        adagrad_row<EPL, VecRows>(a.V, a.AV, r, a.d, gl, 0, x, acc, g, a.lr, a.clip != 0, a.clip_norm);
     if (gl == 0) {
         a.cntV[r] = 0;
         a.cntP[r] = 0;
@@ -2899,163 +2883,143 @@ static int epl_for(int d) {
     return e <= 1 ? 1 : e <= 2 ? 2 : e <= 4 ? 4 : e <= 8 ? 8 : 16;
 }
 
-// GBPR at d <= 64 (EPL <= 4): two pairs per 16-lane group keep more rows of
-// the 10M-user / 1M-item tables in flight (cfg4 grad 164.9 -> 157.6 us); at
-// d = 128 the second pair's registers cost occupancy (cfg5 AMF 148 -> 253 us)
-
-// the LDS-staged W = 5 kernel (grad_lds_kernel): grad_path 3, or auto where
-// it applies -- BPR / AMF / CML at d = 128, GBPR (G = 1) at d = 64; one pair
-// per 16-lane group, 16 per block
-static bool lds_path(const StepArgs& a) {
-    if (a.apr) return false;   // AMF apr: the generic kernel (apr_pair)
-    const bool want = a.grad_path == 3 || a.grad_path == 0;
-    if (!want || a.W != 5 || a.srec != nullptr) return false;
-    if (a.model == BPR || a.model == AMF || a.model == CML) return a.d == 128;
-    if (a.model == GBPR) return a.d == 64 && a.G == 1;
-    return false;
-}
-
-// which grad kernel a step takes (see launch_grad_m): 1 = W=1 fast, 5 = W=5
-// fast (or the LDS-staged kernel), 0 = generic
-static int fast_w(const StepArgs& a) {
-    if (a.apr) return 0;   // AMF apr: the generic kernel (apr_pair)
-    if (lds_path(a)) return 5;
-    // CML at W = 5 keeps five distance rows and the clip live per pair: the
-    // generic kernel measured faster than the phased one there (cfg3: 160 vs
-    // 184 us), so auto (grad_path 0) leaves it on the generic kernel unless
-    // the LDS-staged kernel applies; 2 forces the phased kernel
-    const bool ok = a.grad_path != 1 && epl_for(a.d) <= 8 && (a.model != GBPR || a.G == 1) &&
-                    !(a.grad_path == 0 && a.model == CML && a.W == 5);
-    return ok && (a.W == 1 || a.W == 5) ? a.W : 0;
-}
-
-static int prep_blocks(const StepArgs* nx) {
-    if (!nx || nx->B <= 0) return 0;
-    const int ppb = prep_pairs_per_block(*nx);
-    return (nx->B + ppb - 1) / ppb;
-}
-
-template <int MODEL, int WT, bool DRAW>
-static hipError_t launch_grad_w_d(const StepArgs& a, const StepArgs& n, int ng, int np, hipStream_t s) {
-    const dim3 grid(ng + np), block(kBlock);
-    switch (epl_for(a.d)) {
-        case 1: hipLaunchKernelGGL((grad_kernel<MODEL, 1, WT, DRAW>), grid, block, 0, s, a, n, ng, np); break;
-        case 2: hipLaunchKernelGGL((grad_kernel<MODEL, 2, WT, DRAW>), grid, block, 0, s, a, n, ng, np); break;
-        case 4: hipLaunchKernelGGL((grad_kernel<MODEL, 4, WT, DRAW>), grid, block, 0, s, a, n, ng, np); break;
-        case 8: hipLaunchKernelGGL((grad_kernel<MODEL, 8, WT, DRAW>), grid, block, 0, s, a, n, ng, np); break;
-        default: hipLaunchKernelGGL((grad_kernel<MODEL, 16, WT, DRAW>), grid, block, 0, s, a, n, ng, np); break;
+// The one dispatch on the row width: calls f(std::integral_constant<int, E>{})
+// with E = epl_for(d) slots per lane and returns the launch's error.  A
+// launcher whose kernels stop at d = 128 passes MAX_EPL = 8 (its callers have
+// ruled out wider rows), and every wider d takes E = MAX_EPL.
+template <int MAX_EPL = 16, class F>
+static hipError_t with_epl(int d, F&& f) {
+    static_assert(MAX_EPL == 8 || MAX_EPL == 16, "the widths kernels are built for end at 8 or 16");
+    switch (epl_for(d)) {
+        case 1: f(std::integral_constant<int, 1>{}); break;
+        case 2: f(std::integral_constant<int, 2>{}); break;
+        case 4: f(std::integral_constant<int, 4>{}); break;
+        case 8: f(std::integral_constant<int, 8>{}); break;
+        default: f(std::integral_constant<int, MAX_EPL>{}); break;
     }
     return hipGetLastError();
+}
+
+// The gradient launchers.  Which kernel a step takes and its grid are decided
+// once, by grad_plan (cf_kernels.hip): launch_grad hands the plan down and
+// every launcher below takes its branch, its compile-time W and its block
+// counts from it -- plan.blocks is also the number of loss partials the
+// engine folds, so nothing here derives a grid of its own.
+
+// grad_kernel, the generic kernel (and PLR's); DRAW: with the next step's
+// draw blocks (pipeline 2)
+template <int MODEL, int WT>
+static hipError_t launch_grad_w(const StepArgs& a, const StepArgs* nx, const GradPlan& pl, hipStream_t s) {
+    const int ng = pl.blocks, np = pl.draw_blocks;
+    const StepArgs n = nx ? *nx : a;
+    const dim3 grid(ng + np), block(kBlock);
+    if (np > 0)
+        return with_epl(a.d, [&](auto e) {
+            hipLaunchKernelGGL((grad_kernel<MODEL, decltype(e)::value, WT, true>), grid, block, 0, s, a, n, ng, np);
+        });
+    return with_epl(a.d, [&](auto e) {
+        hipLaunchKernelGGL((grad_kernel<MODEL, decltype(e)::value, WT, false>), grid, block, 0, s, a, n, ng, 0);
+    });
+}
+
+// grad_sort_kernel (pos_sort); FX: the deterministic fixed-point form; DRAW:
+// with the next step's draw blocks (pipeline 3).  FULL (d == 16 * EPL) exists
+// at widths 4 and 8 and is launched at 4 and, without FX, at 8
+template <int MODEL, int WT, bool FX, bool DRAW>
+static hipError_t launch_sort_e(const StepArgs& a, const StepArgs& n, int ng, int np, hipStream_t s) {
+    const dim3 grid(ng + np), block(kBlock);
+    const bool full = a.d == kGL * epl_for(a.d);
+    return with_epl<8>(a.d, [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        if constexpr (E >= 4) {
+            if (full && !(E == 8 && FX)) {
+                hipLaunchKernelGGL((grad_sort_kernel<MODEL, E, WT, FX, true, DRAW>), grid, block, 0, s, a, n, ng, np);
+                return;
+            }
+        }
+        hipLaunchKernelGGL((grad_sort_kernel<MODEL, E, WT, FX, false, DRAW>), grid, block, 0, s, a, n, ng, np);
+    });
 }
 
 template <int MODEL, int WT>
-static hipError_t launch_grad_w(const StepArgs& a, const StepArgs* nx, hipStream_t s) {
-    const int ng = (a.B + kPairsPerBlock - 1) / kPairsPerBlock, np = prep_blocks(nx);
+static hipError_t launch_grad_sorted(const StepArgs& a, const StepArgs* nx, const GradPlan& pl, hipStream_t s) {
+    const int ng = pl.blocks, np = pl.draw_blocks;
     const StepArgs n = nx ? *nx : a;
-    return np > 0 ? launch_grad_w_d<MODEL, WT, true>(a, n, ng, np, s)
-                  : launch_grad_w_d<MODEL, WT, false>(a, n, ng, 0, s);
+    if (np > 0)
+        return a.det_fx ? launch_sort_e<MODEL, WT, true, true>(a, n, ng, np, s)
+                        : launch_sort_e<MODEL, WT, false, true>(a, n, ng, np, s);
+    return a.det_fx ? launch_sort_e<MODEL, WT, true, false>(a, n, ng, 0, s)
+                    : launch_sort_e<MODEL, WT, false, false>(a, n, ng, 0, s);
 }
 
-// grad_sort_kernel by row width; FX: the deterministic fixed-point form;
-// DRAW: with the next step's draw blocks (pipeline 3)
-template <int MODEL, int WT, bool FX, bool DRAW>
-static hipError_t launch_sort_e(const StepArgs& a, const StepArgs& n, int ng, int np, dim3 grid, bool full,
-                                hipStream_t s) {
-    const dim3 block(kBlock);
-    switch (epl_for(a.d)) {
-        case 1: hipLaunchKernelGGL((grad_sort_kernel<MODEL, 1, WT, FX, false, DRAW>), grid, block, 0, s, a, n, ng, np); break;
-        case 2: hipLaunchKernelGGL((grad_sort_kernel<MODEL, 2, WT, FX, false, DRAW>), grid, block, 0, s, a, n, ng, np); break;
-        case 4:
-            if (full) hipLaunchKernelGGL((grad_sort_kernel<MODEL, 4, WT, FX, true, DRAW>), grid, block, 0, s, a, n, ng, np);
-            else hipLaunchKernelGGL((grad_sort_kernel<MODEL, 4, WT, FX, false, DRAW>), grid, block, 0, s, a, n, ng, np);
-            break;
-        default:
-            if (full && !FX) hipLaunchKernelGGL((grad_sort_kernel<MODEL, 8, WT, FX, true, DRAW>), grid, block, 0, s, a, n, ng, np);
-            else hipLaunchKernelGGL((grad_sort_kernel<MODEL, 8, WT, FX, false, DRAW>), grid, block, 0, s, a, n, ng, np);
-            break;
-    }
-    return hipGetLastError();
-}
-
+// grad_fast_kernel, the phased kernel with P pairs per 16-lane group (a
+// sorted plan: its pos_sort form above); DRAW: with the next step's draw
+// blocks (pipeline 2); FULL exists at width 4 without the draw
 template <int MODEL, int WT, int P>
-static hipError_t launch_grad_fast(const StepArgs& a, const StepArgs* nx, hipStream_t s) {
-    // the grid must match grad_blocks(): P * kGroupsPerBlock pairs per block
-    const int ng = (a.B + P * kGroupsPerBlock - 1) / (P * kGroupsPerBlock), np = prep_blocks(nx);
+static hipError_t launch_grad_fast(const StepArgs& a, const StepArgs* nx, const GradPlan& pl, hipStream_t s) {
+    if constexpr (MODEL != GBPR && P == 1) {
+        if (pl.kind == kGradSorted) return launch_grad_sorted<MODEL, WT>(a, nx, pl, s);
+    }
+    if (pl.kind != kGradPhased) return hipErrorInvalidValue;
+    const int ng = pl.blocks, np = pl.draw_blocks;
     const StepArgs n = nx ? *nx : a;
     const dim3 grid(ng + np), block(kBlock);
-    if constexpr (MODEL != GBPR && P == 1) {
-        if (a.srec != nullptr) {   // pos_sort; with nx (pipeline 3) the next draw rides along
-            const int sg = (a.B + CF_SORT_TILES * kPsortPPB - 1) / (CF_SORT_TILES * kPsortPPB);
-            const dim3 sgrid(sg + np);
-            const bool full = a.d == kGL * epl_for(a.d);
-            if (np > 0)
-                return a.det_fx ? launch_sort_e<MODEL, WT, true, true>(a, n, sg, np, sgrid, full, s)
-                                : launch_sort_e<MODEL, WT, false, true>(a, n, sg, np, sgrid, full, s);
-            return a.det_fx ? launch_sort_e<MODEL, WT, true, false>(a, n, sg, 0, sgrid, full, s)
-                            : launch_sort_e<MODEL, WT, false, false>(a, n, sg, 0, sgrid, full, s);
+    if (np > 0)
+        return with_epl<8>(a.d, [&](auto e) {
+            hipLaunchKernelGGL((grad_fast_kernel<MODEL, decltype(e)::value, WT, P, true>), grid, block, 0, s, a, n, ng, np);
+        });
+    const bool full = a.d == kGL * epl_for(a.d);
+    return with_epl<8>(a.d, [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        if constexpr (E == 4) {
+            if (full) {
+                hipLaunchKernelGGL((grad_fast_kernel<MODEL, 4, WT, P, false, false, true>), grid, block, 0, s, a, n, ng, 0);
+                return;
+            }
         }
-    }
-    if (a.srec != nullptr) return hipErrorInvalidValue;
-    if (np > 0) {
-        switch (epl_for(a.d)) {
-            case 1: hipLaunchKernelGGL((grad_fast_kernel<MODEL, 1, WT, P, true>), grid, block, 0, s, a, n, ng, np); break;
-            case 2: hipLaunchKernelGGL((grad_fast_kernel<MODEL, 2, WT, P, true>), grid, block, 0, s, a, n, ng, np); break;
-            case 4: hipLaunchKernelGGL((grad_fast_kernel<MODEL, 4, WT, P, true>), grid, block, 0, s, a, n, ng, np); break;
-            default: hipLaunchKernelGGL((grad_fast_kernel<MODEL, 8, WT, P, true>), grid, block, 0, s, a, n, ng, np); break;
-        }
-    } else {
-        const bool full = a.d == kGL * epl_for(a.d);
-        switch (epl_for(a.d)) {
-            case 1: hipLaunchKernelGGL((grad_fast_kernel<MODEL, 1, WT, P, false>), grid, block, 0, s, a, n, ng, 0); break;
-            case 2: hipLaunchKernelGGL((grad_fast_kernel<MODEL, 2, WT, P, false>), grid, block, 0, s, a, n, ng, 0); break;
-            case 4:
-                if (full) hipLaunchKernelGGL((grad_fast_kernel<MODEL, 4, WT, P, false, false, true>), grid, block, 0, s, a, n, ng, 0);
-                else hipLaunchKernelGGL((grad_fast_kernel<MODEL, 4, WT, P, false>), grid, block, 0, s, a, n, ng, 0);
-                break;
-            default: hipLaunchKernelGGL((grad_fast_kernel<MODEL, 8, WT, P, false>), grid, block, 0, s, a, n, ng, 0); break;
-        }
-    }
-    return hipGetLastError();
+        hipLaunchKernelGGL((grad_fast_kernel<MODEL, E, WT, P, false>), grid, block, 0, s, a, n, ng, 0);
+    });
 }
 
-// W = 1 (BPRMF driver) and W = 5 (AMF / CML / GBPR drivers) with G <= 1 and
-// d <= 128 take the phased fast path; anything else the generic kernel
 // tuple ranking: prefetched tuples of width 4 (CPLR, W = 2) or 5 (PRIGP, W = 3)
-static hipError_t launch_grad_plr(const StepArgs& a, hipStream_t s) {
-    if (a.W == 2) return launch_grad_w<PLR, 2>(a, nullptr, s);
-    if (a.W == 3) return launch_grad_w<PLR, 3>(a, nullptr, s);
+static hipError_t launch_grad_plr(const StepArgs& a, const GradPlan& pl, hipStream_t s) {
+    if (pl.wt == 2) return launch_grad_w<PLR, 2>(a, nullptr, pl, s);
+    if (pl.wt == 3) return launch_grad_w<PLR, 3>(a, nullptr, pl, s);
     return hipErrorInvalidValue;
 }
 
 template <int MODEL>
-static hipError_t launch_grad_m(const StepArgs& a, const StepArgs* nx, hipStream_t s) {
-    const int e = epl_for(a.d);
-    if constexpr (MODEL == BPR || MODEL == AMF || MODEL == CML || MODEL == GBPR) {
-        // a fused draw (pipeline 2) takes the phased kernel (grad_blocks with
-        // the draw counts its grid)
-        if (lds_path(a) && prep_blocks(nx) == 0) {
-            const dim3 grid((a.B + kGroupsPerBlock - 1) / kGroupsPerBlock), block(kBlock);
+static hipError_t launch_grad_m(const StepArgs& a, const StepArgs* nx, const GradPlan& pl, hipStream_t s) {
+    static_assert(MODEL == BPR || MODEL == AMF || MODEL == CML || MODEL == GBPR, "tuples take launch_grad_plr");
+    switch (pl.kind) {
+        case kGradLds: {
+            const dim3 grid(pl.blocks), block(kBlock);
             if constexpr (MODEL == GBPR)
                 hipLaunchKernelGGL((grad_lds_kernel<GBPR, 4, 5>), grid, block, 0, s, a);
             else
                 hipLaunchKernelGGL((grad_lds_kernel<MODEL, 8, 5>), grid, block, 0, s, a);
             return hipGetLastError();
         }
+        case kGradSorted:
+        case kGradPhased:
+            if (pl.wt == 1) return launch_grad_fast<MODEL, 1, CF_FAST_PAIRS_W1>(a, nx, pl, s);
+            if (pl.kind == kGradPhased && pl.pairs_per_block == CF_FAST_PAIRS_GBPR_W5 * kGroupsPerBlock)
+                return launch_grad_fast<MODEL, 5, CF_FAST_PAIRS_GBPR_W5>(a, nx, pl, s);
+            return launch_grad_fast<MODEL, 5, CF_FAST_PAIRS_W5>(a, nx, pl, s);
+        case kGradGeneric:
+            if (pl.wt == 1) return launch_grad_w<MODEL, 1>(a, nx, pl, s);
+            if (pl.wt == 5) return launch_grad_w<MODEL, 5>(a, nx, pl, s);
+            return launch_grad_w<MODEL, 0>(a, nx, pl, s);
+        default:
+            return hipErrorInvalidValue;   // apr is launch_grad_amf's; kGradNone has no kernel
     }
-    const int fw = fast_w(a);
-    if (fw == 1) return launch_grad_fast<MODEL, 1, CF_FAST_PAIRS_W1>(a, nx, s);
-    if (fw == 5 && MODEL == GBPR && e <= 4) return launch_grad_fast<MODEL, 5, CF_FAST_PAIRS_GBPR_W5>(a, nx, s);
-    if (fw == 5) return launch_grad_fast<MODEL, 5, CF_FAST_PAIRS_W5>(a, nx, s);
-    if (a.W == 1) return launch_grad_w<MODEL, 1>(a, nx, s);
-    if (a.W == 5 && e <= 8) return launch_grad_w<MODEL, 5>(a, nx, s);
-    return launch_grad_w<MODEL, 0>(a, nx, s);
 }
 
 // one gradient launcher per model, each in its own translation unit
-hipError_t launch_grad_bpr(const StepArgs& a, const StepArgs* nx, hipStream_t s);
-hipError_t launch_grad_amf(const StepArgs& a, const StepArgs* nx, hipStream_t s);
-hipError_t launch_grad_cml(const StepArgs& a, const StepArgs* nx, hipStream_t s);
-hipError_t launch_grad_gbpr(const StepArgs& a, const StepArgs* nx, hipStream_t s);
-hipError_t launch_grad_plr_t(const StepArgs& a, hipStream_t s);
+hipError_t launch_grad_bpr(const StepArgs& a, const StepArgs* nx, const GradPlan& pl, hipStream_t s);
+hipError_t launch_grad_amf(const StepArgs& a, const StepArgs* nx, const GradPlan& pl, hipStream_t s);
+hipError_t launch_grad_cml(const StepArgs& a, const StepArgs* nx, const GradPlan& pl, hipStream_t s);
+hipError_t launch_grad_gbpr(const StepArgs& a, const StepArgs* nx, const GradPlan& pl, hipStream_t s);
+hipError_t launch_grad_plr_t(const StepArgs& a, const GradPlan& pl, hipStream_t s);
 
 }  // namespace cfk

@@ -419,7 +419,8 @@ int cf_xchg_finish(cf_engine* eng, int64_t n_recv);
  * keys its committed PMC counters by it; tests assert the path under test):
  * a bitmask of cf_path_flag, plus the pipeline option in bits 8-9. */
 enum cf_path_flag {
-    CF_PATH_PHASED = 1,         /* phased gradient kernel (grad_fast_kernel), else generic */
+    CF_PATH_PHASED = 1,         /* phased gradient kernel (grad_fast_kernel), else generic
+                                   (amf_mode apr in the adversarial phase: generic)        */
     CF_PATH_POS_SORT = 2,       /* positive-sorted gradient (psort + partial rows)         */
     CF_PATH_ITEM_RECORDS = 4,   /* item records + user-row stash instead of slot rows      */
     CF_PATH_DETERMINISTIC = 8,  /* sort-based ranks, compact slots, no float atomics       */
