@@ -24,7 +24,7 @@ import numpy as np
 from . import _native as N
 from .engine import Engine
 from .io_util import to_csr
-from .ranking import evaluateCV, evaluateLOOV
+from .ranking import evaluateCV, evaluateLOOV, scores_from_sums
 
 
 def parse_device(device):
@@ -57,6 +57,7 @@ class PairwiseModel(object):
         self._engine = None
         self._train_lr = float(lr)  # the value the optimizer is built with
         self._init_tables = None
+        self._device_eval = False
 
     # ---- hooks ----------------------------------------------------------------
     def _engine_kwargs(self):
@@ -135,6 +136,10 @@ class PairwiseModel(object):
                 eng.set_table(name, arr)
         if device_fed:
             eng.set_sampler_state(*sampler.state())
+        device_eval = self._device_eval and self._split_method in ("cv", "loov")
+        if device_eval:
+            eng.set_truth(t_indptr, t_indices)
+            eval_users = np.asarray(test_users, dtype=np.int32)
 
         scores = None
         for it in range(self._max_iter):
@@ -150,8 +155,12 @@ class PairwiseModel(object):
                     eng.step(*batch, return_loss=False)
                 aveloss = eng.take_loss() / max(n_batches, 1)
             timecost = time.time() - t0
-            yss_pred = self._recommend(test_users)
-            scores = self._eval(yss_true, yss_pred)
+            if device_eval:
+                sums = eng.evaluate(eval_users, [self._topN], exclude_train=True)
+                scores = scores_from_sums(sums[0], len(test_users), self._eval_metrics, self._split_method)
+            else:
+                yss_pred = self._recommend(test_users)
+                scores = self._eval(yss_true, yss_pred)
             if self._verbose:
                 print(self._log_line(fold, it, aveloss, scores, timecost))
                 sys.stdout.flush()
@@ -179,3 +188,9 @@ class PairwiseModel(object):
             if arr is not None:
                 t[name] = np.asarray(arr, dtype=np.float32)
         self._init_tables = t or None
+
+    def set_device_eval(self, on=True):
+        """Evaluate each epoch on the device (Engine.evaluate at [topN]: the
+        lists never reach the host) instead of _recommend + ranking.py.  Off
+        by default; the scores agree to fp64 summation order."""
+        self._device_eval = bool(on)

@@ -1,11 +1,12 @@
 // cf_engine.cpp -- host side of the C ABI declared in include/cf_engine.h.
 // Owns the device tables, the HBM-resident interaction graph, the device
 // sampler position and the HIP stream; enqueues the gfx950 kernels of
-// cf_kernels.hip / cf_eval.hip.  No exception crosses the ABI.
+// cf_kernels.hip / cf_eval.hip / cf_metrics.hip.  No exception crosses the ABI.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <atomic>
+#include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
@@ -317,6 +318,17 @@ struct cf_engine {
     // eval workspace
     DevBuf<uint32_t> keys;
     DevBuf<uint64_t> item_mask;   // cf_score_topk's caller mask, one bit per item
+    // device metrics (cf_set_truth / cf_eval_lists / cf_evaluate): the truth
+    // CSR, its host row pointers (an empty row is rejected without a sync),
+    // the discount table and the reduction's workspace
+    bool truth_set = false;
+    DevBuf<int64_t> t_indptr;
+    DevBuf<int32_t> t_indices;
+    std::vector<int64_t> h_tindptr;
+    DevBuf<double> disc;       // [kEvalMaxK] 1 / log2(p + 2)
+    DevBuf<double> ev_rows;    // [n, n_cut, kEvalN] when the caller's per-user output is not device memory
+    DevBuf<double> ev_part;    // [metrics_partials(n), n_cut * kEvalN]
+    DevBuf<double> ev_sums;    // [kEvalMaxCut * kEvalN]
 
     int topk_path = 0;  // cf_set_option("topk_path")
     int fused_variant = 0;  // cf_set_option("fused_variant")
@@ -1482,15 +1494,14 @@ float** table_slot(cf_engine* e, int t) {
     }
 }
 
+// The device-resident recommend pass shared by cf_score_topk_ex and
+// cf_evaluate: d_users [n] -> d_idx [n, k] (d_val [n, k], nullable), all device
+// memory, enqueued on the engine stream; the caller synchronises.
+
 // fused fp32-MFMA scoring + streaming top-k: no score matrix in HBM
-int score_topk_fused(cf_engine* e, const int32_t* users, int n, int k, int exclude_train,
-                     const uint64_t* item_mask, int32_t* idx_out, float* val_out) {
+int topk_fused_device(cf_engine* e, const int32_t* d_users, int n, int k, int exclude_train,
+                      const uint64_t* item_mask, int32_t* d_idx, float* d_val) {
     const cf_config& c = e->cfg;
-    DevBuf<int32_t> d_users, d_idx;
-    DevBuf<float> d_val;
-    CF_TRY(d_users.reset((size_t)n, "top-k users"));
-    CF_TRY(d_idx.reset((size_t)n * k, "top-k indices"));
-    if (val_out) CF_TRY(d_val.reset((size_t)n * k, "top-k values"));
     FusedTopkArgs f{};
     f.model = c.model == CF_PLR ? CF_GBPR : c.model;  // U.V^T + b (prigp.py:137, cplr_u.py:146)
     f.d = c.n_factors;
@@ -1510,7 +1521,7 @@ int score_topk_fused(cf_engine* e, const int32_t* users, int n, int k, int exclu
     f.val_out = d_val;
     f.variant = e->fused_variant;
     f.item_mask = item_mask;
-    hipError_t he = hipMemcpyAsync(d_users, users, (size_t)n * 4, hipMemcpyHostToDevice, e->stream);
+    hipError_t he = hipSuccess;
 #ifdef CF_FUSED_STAMPS
     // diagnostic builds: per-wave cycles of each phase of the sweep, summed
     // over the waves and printed (tools/score_ab.py)
@@ -1519,14 +1530,14 @@ int score_topk_fused(cf_engine* e, const int32_t* users, int n, int k, int exclu
     DevBuf<unsigned long long> d_st;
     CF_TRY(d_st.reset(n_st, "fused stamps"));
     f.stamps = d_st;
-    if (he == hipSuccess) he = hipMemsetAsync(f.stamps, 0, n_st * sizeof(unsigned long long), e->stream);
+    he = hipMemsetAsync(f.stamps, 0, n_st * sizeof(unsigned long long), e->stream);
 #endif
     if (he == hipSuccess) {
         ProfScope ps(e, CF_K_TOPK);
         he = launch_fused_topk(f, e->stream);
     }
-    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
 #ifdef CF_FUSED_STAMPS
+    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
     if (he == hipSuccess) he = hipMemcpy(h_st.data(), f.stamps, n_st * sizeof(unsigned long long), hipMemcpyDefault);
     if (he == hipSuccess) {
         static const char* names[14] = {"stage", "bar1", "mfma", "cand_rest", "bar2", "tile_wait", "store",
@@ -1543,11 +1554,64 @@ int score_topk_fused(cf_engine* e, const int32_t* users, int n, int k, int exclu
                 std::fprintf(stderr, "fused stamps: %-14s %.4e  %.3f\n", names[q], tot[q], tot[q] / all);
     }
 #endif
-    if (he == hipSuccess) he = hipMemcpy(idx_out, d_idx, (size_t)n * k * 4, hipMemcpyDefault);
-    if (he == hipSuccess && val_out)
-        he = hipMemcpy(val_out, d_val, (size_t)n * k * 4, hipMemcpyDefault);
     if (he != hipSuccess) return fail(CF_EHIP, std::string("cf_score_topk (fused): ") + hipGetErrorString(he));
     return CF_OK;
+}
+
+// scores materialised per user chunk + radix select
+int topk_materialised_device(cf_engine* e, const int32_t* d_users, int n, int k, int exclude_train,
+                             const uint64_t* item_mask, int32_t* d_idx, float* d_val) {
+    const cf_config& c = e->cfg;
+    const size_t row_bytes = (size_t)c.n_items * 4;
+    const size_t budget = (size_t)512 << 20;
+    int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, budget / row_bytes));
+    CF_TRY(e->keys.reserve((size_t)chunk * c.n_items, "score keys"));
+    hipError_t he = hipSuccess;
+    for (int u0 = 0; he == hipSuccess && u0 < n; u0 += chunk) {
+        const int m = std::min(chunk, n - u0);
+        ScoreArgs s{};
+        s.model = c.model == CF_PLR ? CF_GBPR : c.model;
+        s.d = c.n_factors;
+        s.n_users = m;
+        s.n_items = c.n_items;
+        s.users = d_users + u0;
+        s.U = e->U;
+        s.V = e->V;
+        s.b = e->b;
+        s.keys = e->keys;
+        s.exclude_train = exclude_train ? 1 : 0;
+        s.indptr = e->indptr;
+        s.indices = e->indices;
+        s.item_mask = item_mask;
+        {
+            ProfScope ps(e, CF_K_SCORE);
+            he = launch_score(s, e->stream);
+        }
+        if (he != hipSuccess) break;
+        TopkArgs t{};
+        t.k = k;
+        t.n_items = c.n_items;
+        t.keys = e->keys;
+        t.idx_out = d_idx + (size_t)u0 * k;
+        t.val_out = d_val ? d_val + (size_t)u0 * k : nullptr;
+        {
+            ProfScope ps(e, CF_K_TOPK);
+            he = launch_topk(t, m, e->stream);
+        }
+    }
+    if (he != hipSuccess) return fail(CF_EHIP, std::string("cf_score_topk: ") + hipGetErrorString(he));
+    return CF_OK;
+}
+
+// the path "topk_path" picks for (k, n_factors)
+int topk_device(cf_engine* e, const int32_t* d_users, int n, int k, int exclude_train, const uint64_t* item_mask,
+                int32_t* d_idx, float* d_val) {
+    const bool fused_ok = k <= kFusedMaxWideK && e->cfg.n_factors <= kFusedMaxD;
+    if (e->topk_path == 2 && !fused_ok)
+        return fail(CF_EINVAL, "fused top-k needs k <= 128 and n_factors <= 128");
+    if (fused_ok && e->topk_path != 1)
+        return topk_fused_device(e, d_users, n, k, exclude_train, item_mask, d_idx, d_val);
+    return topk_materialised_device(e, d_users, n, k, exclude_train, item_mask, d_idx, d_val);
 }
 
 }  // namespace
@@ -2707,95 +2771,258 @@ int cf_score_topk(cf_engine* e, const int32_t* users, int32_t n, int32_t k, cons
     return cf_score_topk_ex(e, users, n, k, mask_or_NULL ? 0 : 1, mask_or_NULL, idx_out, val_out);
 }
 
+namespace {
+
+// the caller's item mask (uint8 [n_items], host or device) as one bit per
+// item, 64 items per word -- the fused kernel ORs one word into each
+// 64-item tile's exclusion mask, the materialised path zeroes the keys
+int stage_item_mask(cf_engine* e, const uint8_t* item_mask, const uint64_t** d_mask) {
+    *d_mask = nullptr;
+    if (!item_mask) return CF_OK;
+    const cf_config& c = e->cfg;
+    const int64_t nw = (c.n_items + 63) / 64;
+    std::vector<uint8_t> hm;
+    if (is_device_ptr(item_mask)) {
+        hm.resize((size_t)c.n_items);
+        CF_HIP(hipMemcpy(hm.data(), item_mask, (size_t)c.n_items, hipMemcpyDeviceToHost));
+        item_mask = hm.data();
+    }
+    std::vector<uint64_t> bits((size_t)nw, 0ull);
+    for (int64_t j = 0; j < c.n_items; ++j)
+        if (item_mask[j]) bits[(size_t)(j >> 6)] |= 1ull << (j & 63);
+    CF_TRY(e->item_mask.reserve((size_t)nw, "item mask"));
+    CF_HIP(hipMemcpyAsync(e->item_mask, bits.data(), (size_t)nw * 8, hipMemcpyHostToDevice, e->stream));
+    CF_HIP(hipStreamSynchronize(e->stream));   // `bits` is pageable and local
+    *d_mask = e->item_mask;
+    return CF_OK;
+}
+
+// users [n] (host or device) range-checked from host memory: *users is left
+// pointing at host ids (device ids, e.g. torch: a host copy in `keep`)
+int checked_host_users(cf_engine* e, const int32_t** users, int n, std::vector<int32_t>& keep) {
+    if (is_device_ptr(*users)) {
+        keep.resize((size_t)n);
+        CF_HIP(hipMemcpy(keep.data(), *users, (size_t)n * 4, hipMemcpyDeviceToHost));
+        *users = keep.data();
+    }
+    for (int r = 0; r < n; ++r)
+        if ((*users)[r] < 0 || (*users)[r] >= e->cfg.n_users) return fail(CF_EINVAL, "user id out of range");
+    return CF_OK;
+}
+
+// cf_eval_lists / cf_evaluate: truth, cutoffs (the last <= k where k > 0) and outputs
+int check_eval_args(cf_engine* e, const int32_t* users, int32_t n, const int32_t* cutoffs, int32_t n_cut, int32_t k,
+                    const double* sums_out) {
+    if (!e->truth_set) return fail(CF_ESTATE, "no truth: call cf_set_truth first");
+    if (n < 0 || !sums_out || !cutoffs || (n > 0 && !users)) return fail(CF_EINVAL, "bad arguments");
+    if (n_cut < 1 || n_cut > kEvalMaxCut) return fail(CF_EINVAL, "n_cut must be 1..8");
+    for (int q = 0; q < n_cut; ++q) {
+        if (cutoffs[q] < 1 || cutoffs[q] > kEvalMaxK) return fail(CF_EINVAL, "cutoffs must be 1..4096");
+        if (q > 0 && cutoffs[q] <= cutoffs[q - 1]) return fail(CF_EINVAL, "cutoffs must be strictly ascending");
+    }
+    if (k > 0 && cutoffs[n_cut - 1] > k) return fail(CF_EINVAL, "the last cutoff exceeds the list width k");
+    return CF_OK;
+}
+
+// map_k_score divides by len(truth) (ranking.py:43-56): a user needs a truth item
+int check_truth_rows(cf_engine* e, const int32_t* host_users, int n) {
+    for (int r = 0; r < n; ++r) {
+        const int32_t u = host_users[r];
+        if (e->h_tindptr[(size_t)u + 1] == e->h_tindptr[(size_t)u])
+            return fail(CF_EINVAL, "user " + std::to_string(u) + " has an empty truth row");
+    }
+    return CF_OK;
+}
+
+// The metric launches on device lists d_idx [n, k] of d_users [n]: per-user
+// rows into d_rows (the caller's device per_user_out, else engine scratch),
+// their fixed-order sums into e->ev_sums.  Enqueued; the caller synchronises.
+int metrics_device(cf_engine* e, const int32_t* d_users, int n, const int32_t* d_idx, int k,
+                   const int32_t* cutoffs, int n_cut, double* d_rows) {
+    MetricsArgs m{};
+    m.n = n;
+    m.n_users = e->cfg.n_users;
+    m.k = k;
+    m.n_cut = n_cut;
+    for (int q = 0; q < kEvalMaxCut; ++q) m.cutoffs[q] = q < n_cut ? cutoffs[q] : cutoffs[n_cut - 1];
+    m.users = d_users;
+    m.idx = d_idx;
+    m.t_indptr = e->t_indptr;
+    m.t_indices = e->t_indices;
+    m.disc = e->disc;
+    m.per_user = d_rows;
+    CF_TRY(e->ev_part.reserve((size_t)metrics_partials(n) * n_cut * kEvalN, "metric partials"));
+    CF_TRY(e->ev_sums.reserve((size_t)kEvalMaxCut * kEvalN, "metric sums"));
+    m.partial = e->ev_part;
+    m.sums = e->ev_sums;
+    hipError_t he;
+    {
+        ProfScope ps(e, CF_K_METRICS);
+        he = launch_metrics(m, e->stream);
+    }
+    if (he != hipSuccess) return fail(CF_EHIP, std::string("metrics: ") + hipGetErrorString(he));
+    return CF_OK;
+}
+
+// where the per-user rows are written: the caller's buffer when it is device
+// memory, else engine scratch (copied out by eval_finish)
+int eval_rows(cf_engine* e, int n, int n_cut, double* per_user_out, double** d_rows) {
+    if (per_user_out && is_device_ptr(per_user_out)) {
+        *d_rows = per_user_out;
+        return CF_OK;
+    }
+    CF_TRY(e->ev_rows.reserve((size_t)n * n_cut * kEvalN, "per-user metric rows"));
+    *d_rows = e->ev_rows;
+    return CF_OK;
+}
+
+int eval_finish(cf_engine* e, int n, int n_cut, const double* d_rows, double* sums_out, double* per_user_out) {
+    CF_HIP(hipStreamSynchronize(e->stream));
+    CF_HIP(hipMemcpy(sums_out, e->ev_sums, (size_t)n_cut * kEvalN * 8, hipMemcpyDeviceToHost));
+    if (per_user_out && per_user_out != d_rows)
+        CF_HIP(hipMemcpy(per_user_out, d_rows, (size_t)n * n_cut * kEvalN * 8, hipMemcpyDeviceToHost));
+    return CF_OK;
+}
+
+}  // namespace
+
 int cf_score_topk_ex(cf_engine* e, const int32_t* users, int32_t n, int32_t k, int32_t exclude_train,
                      const uint8_t* item_mask, int32_t* idx_out, float* val_out) {
     CF_TRY(check_engine(e));
-    const cf_config& c = e->cfg;
     if (n < 0 || !idx_out || (n > 0 && !users)) return fail(CF_EINVAL, "bad arguments");
     if (k < 1 || k > 4096) return fail(CF_EINVAL, "k must be 1..4096");
     if (exclude_train && !e->indptr) return fail(CF_ESTATE, "exclude_train needs cf_set_interactions");
     if (n == 0) return CF_OK;
-    // the caller's item mask (uint8 [n_items], host or device) as one bit per
-    // item, 64 items per word -- the fused kernel ORs one word into each
-    // 64-item tile's exclusion mask, the materialised path zeroes the keys
     const uint64_t* d_mask = nullptr;
-    if (item_mask) {
-        const int64_t nw = (c.n_items + 63) / 64;
-        std::vector<uint8_t> hm;
-        if (is_device_ptr(item_mask)) {
-            hm.resize((size_t)c.n_items);
-            CF_HIP(hipMemcpy(hm.data(), item_mask, (size_t)c.n_items, hipMemcpyDeviceToHost));
-            item_mask = hm.data();
-        }
-        std::vector<uint64_t> bits((size_t)nw, 0ull);
-        for (int64_t j = 0; j < c.n_items; ++j)
-            if (item_mask[j]) bits[(size_t)(j >> 6)] |= 1ull << (j & 63);
-        CF_TRY(e->item_mask.reserve((size_t)nw, "item mask"));
-        CF_HIP(hipMemcpyAsync(e->item_mask, bits.data(), (size_t)nw * 8, hipMemcpyHostToDevice, e->stream));
-        CF_HIP(hipStreamSynchronize(e->stream));   // `bits` is pageable and local
-        d_mask = e->item_mask;
-    }
+    CF_TRY(stage_item_mask(e, item_mask, &d_mask));
     std::vector<int32_t> host_users;
-    if (is_device_ptr(users)) {  // device ids (torch): checked from a host copy
-        host_users.resize((size_t)n);
-        CF_HIP(hipMemcpy(host_users.data(), users, (size_t)n * 4, hipMemcpyDeviceToHost));
-        users = host_users.data();
-    }
-    for (int r = 0; r < n; ++r)
-        if (users[r] < 0 || users[r] >= c.n_users) return fail(CF_EINVAL, "user id out of range");
+    CF_TRY(checked_host_users(e, &users, n, host_users));
     CF_HIP(hipStreamSynchronize(e->side));
-    const bool fused_ok = k <= kFusedMaxWideK && c.n_factors <= kFusedMaxD;
-    if (e->topk_path == 2 && !fused_ok)
-        return fail(CF_EINVAL, "fused top-k needs k <= 128 and n_factors <= 128");
-    if (fused_ok && e->topk_path != 1)
-        return score_topk_fused(e, users, n, k, exclude_train, d_mask, idx_out, val_out);
-    const size_t row_bytes = (size_t)c.n_items * 4;
-    const size_t budget = (size_t)512 << 20;
-    int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, budget / row_bytes));
-    CF_TRY(e->keys.reserve((size_t)chunk * c.n_items, "score keys"));
     DevBuf<int32_t> d_users, d_idx;
     DevBuf<float> d_val;
     CF_TRY(d_users.reset((size_t)n, "top-k users"));
     CF_TRY(d_idx.reset((size_t)n * k, "top-k indices"));
-    CF_TRY(d_val.reset((size_t)n * k, "top-k values"));
-    hipError_t he = hipMemcpyAsync(d_users, users, (size_t)n * 4, hipMemcpyHostToDevice, e->stream);
-    for (int u0 = 0; he == hipSuccess && u0 < n; u0 += chunk) {
-        const int m = std::min(chunk, n - u0);
-        ScoreArgs s{};
-        s.model = c.model == CF_PLR ? CF_GBPR : c.model;
-        s.d = c.n_factors;
-        s.n_users = m;
-        s.n_items = c.n_items;
-        s.users = d_users + u0;
-        s.U = e->U;
-        s.V = e->V;
-        s.b = e->b;
-        s.keys = e->keys;
-        s.exclude_train = exclude_train ? 1 : 0;
-        s.indptr = e->indptr;
-        s.indices = e->indices;
-        s.item_mask = d_mask;
-        {
-            ProfScope ps(e, CF_K_SCORE);
-            he = launch_score(s, e->stream);
-        }
-        if (he != hipSuccess) break;
-        TopkArgs t{};
-        t.k = k;
-        t.n_items = c.n_items;
-        t.keys = e->keys;
-        t.idx_out = d_idx + (size_t)u0 * k;
-        t.val_out = d_val + (size_t)u0 * k;
-        {
-            ProfScope ps(e, CF_K_TOPK);
-            he = launch_topk(t, m, e->stream);
+    if (val_out) CF_TRY(d_val.reset((size_t)n * k, "top-k values"));
+    CF_HIP(hipMemcpyAsync(d_users, users, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    CF_TRY(topk_device(e, d_users, n, k, exclude_train, d_mask, d_idx, d_val));
+    CF_HIP(hipStreamSynchronize(e->stream));
+    CF_HIP(hipMemcpy(idx_out, d_idx, (size_t)n * k * 4, hipMemcpyDefault));
+    if (val_out) CF_HIP(hipMemcpy(val_out, d_val, (size_t)n * k * 4, hipMemcpyDefault));
+    return CF_OK;
+}
+
+int cf_set_truth(cf_engine* e, const int64_t* indptr, const int32_t* indices, int64_t nnz) {
+    CF_TRY(check_engine(e));
+    const cf_config& c = e->cfg;
+    if (!indptr || nnz < 0 || (nnz > 0 && !indices)) return fail(CF_EINVAL, "null CSR");
+    // device CSR (torch): validated from a host copy, as the ids of cf_score_topk
+    std::vector<int64_t> hp;
+    std::vector<int32_t> hi;
+    if (is_device_ptr(indptr)) {
+        hp.resize((size_t)c.n_users + 1);
+        CF_HIP(hipMemcpy(hp.data(), indptr, hp.size() * 8, hipMemcpyDeviceToHost));
+        indptr = hp.data();
+    }
+    if (indptr[0] != 0 || indptr[c.n_users] != nnz) return fail(CF_EINVAL, "indptr does not span nnz");
+    if (nnz > 0 && is_device_ptr(indices)) {
+        hi.resize((size_t)nnz);
+        CF_HIP(hipMemcpy(hi.data(), indices, (size_t)nnz * 4, hipMemcpyDeviceToHost));
+        indices = hi.data();
+    }
+    for (int64_t u = 0; u < c.n_users; ++u) {
+        const int64_t rb = indptr[u], re = indptr[u + 1];
+        if (re < rb || re > nnz) return fail(CF_EINVAL, "indptr not monotone");
+        for (int64_t q = rb; q < re; ++q) {
+            const int32_t it = indices[q];
+            if (it < 0 || it >= c.n_items) return fail(CF_EINVAL, "item id out of range");
+            if (q > rb && indices[q - 1] >= it) return fail(CF_EINVAL, "truth rows must be strictly ascending");
         }
     }
-    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-    if (he == hipSuccess) he = hipMemcpy(idx_out, d_idx, (size_t)n * k * 4, hipMemcpyDefault);
-    if (he == hipSuccess && val_out)
-        he = hipMemcpy(val_out, d_val, (size_t)n * k * 4, hipMemcpyDefault);
-    if (he != hipSuccess) return fail(CF_EHIP, std::string("cf_score_topk: ") + hipGetErrorString(he));
+    CF_HIP(hipStreamSynchronize(e->stream));   // a metric launch may still read the old truth
+    e->truth_set = false;
+    CF_TRY(e->t_indptr.reset((size_t)c.n_users + 1, "truth indptr"));
+    CF_TRY(e->t_indices.reset((size_t)nnz + 1, "truth indices"));   // never empty
+    if (!e->disc) {
+        // disc[p] = 1.0 / log2(p + 2.0), the reference's np.log2(pos + 2.0)
+        // (ranking.py:30) with libm's log2; the kernels take no logarithm
+        std::vector<double> disc((size_t)kEvalMaxK);
+        for (int p = 0; p < kEvalMaxK; ++p) disc[(size_t)p] = 1.0 / std::log2((double)p + 2.0);
+        CF_TRY(e->disc.reset((size_t)kEvalMaxK, "discount table"));
+        CF_HIP(hipMemcpy(e->disc, disc.data(), disc.size() * 8, hipMemcpyHostToDevice));
+    }
+    CF_HIP(hipMemcpy(e->t_indptr, indptr, ((size_t)c.n_users + 1) * 8, hipMemcpyHostToDevice));
+    if (nnz > 0) CF_HIP(hipMemcpy(e->t_indices, indices, (size_t)nnz * 4, hipMemcpyHostToDevice));
+    e->h_tindptr.assign(indptr, indptr + c.n_users + 1);
+    e->truth_set = true;
+    return CF_OK;
+}
+
+int cf_eval_lists(cf_engine* e, const int32_t* users, int32_t n, const int32_t* idx, int32_t k,
+                  const int32_t* cutoffs, int32_t n_cut, double* sums_out, double* per_user_out) {
+    CF_TRY(check_engine(e));
+    CF_TRY(check_eval_args(e, users, n, cutoffs, n_cut, k, sums_out));
+    if (k < 1 || (n > 0 && !idx)) return fail(CF_EINVAL, "bad arguments");
+    const int32_t* in_users = users;
+    std::vector<int32_t> host_users;
+    CF_TRY(checked_host_users(e, &users, n, host_users));
+    CF_TRY(check_truth_rows(e, users, n));
+    std::fill(sums_out, sums_out + (size_t)n_cut * kEvalN, 0.0);
+    if (n == 0) return CF_OK;
+    // host inputs are staged; device inputs are read where they sit
+    DevBuf<int32_t> d_users, d_idx;
+    const int32_t* du = in_users;
+    const int32_t* di = idx;
+    if (!is_device_ptr(in_users)) {
+        CF_TRY(d_users.reset((size_t)n, "eval users"));
+        CF_HIP(hipMemcpyAsync(d_users, users, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+        du = d_users;
+    }
+    if (!is_device_ptr(idx)) {
+        CF_TRY(d_idx.reset((size_t)n * k, "eval lists"));
+        CF_HIP(hipMemcpyAsync(d_idx, idx, (size_t)n * k * 4, hipMemcpyHostToDevice, e->stream));
+        di = d_idx;
+    }
+    double* d_rows = nullptr;
+    CF_TRY(eval_rows(e, n, n_cut, per_user_out, &d_rows));
+    int st = metrics_device(e, du, n, di, k, cutoffs, n_cut, d_rows);
+    if (st == CF_OK) st = eval_finish(e, n, n_cut, d_rows, sums_out, per_user_out);
+    if (st != CF_OK) (void)hipStreamSynchronize(e->stream);   // the staged copies read pageable memory
+    return st;
+}
+
+int cf_evaluate(cf_engine* e, const int32_t* users, int32_t n, const int32_t* cutoffs, int32_t n_cut,
+                int32_t exclude_train, const uint8_t* item_mask, double* sums_out, double* per_user_out,
+                int32_t* idx_out) {
+    CF_TRY(check_engine(e));
+    CF_TRY(check_eval_args(e, users, n, cutoffs, n_cut, 0, sums_out));
+    if (exclude_train && !e->indptr) return fail(CF_ESTATE, "exclude_train needs cf_set_interactions");
+    const int k = cutoffs[n_cut - 1];
+    std::vector<int32_t> host_users;
+    CF_TRY(checked_host_users(e, &users, n, host_users));
+    CF_TRY(check_truth_rows(e, users, n));
+    std::fill(sums_out, sums_out + (size_t)n_cut * kEvalN, 0.0);
+    if (n == 0) return CF_OK;
+    const uint64_t* d_mask = nullptr;
+    CF_TRY(stage_item_mask(e, item_mask, &d_mask));
+    CF_HIP(hipStreamSynchronize(e->side));
+    DevBuf<int32_t> d_users, d_idx_own;
+    CF_TRY(d_users.reset((size_t)n, "eval users"));
+    int32_t* d_idx = idx_out;   // device lists are written in place
+    if (!idx_out || !is_device_ptr(idx_out)) {
+        CF_TRY(d_idx_own.reset((size_t)n * k, "eval lists"));
+        d_idx = d_idx_own;
+    }
+    double* d_rows = nullptr;
+    CF_TRY(eval_rows(e, n, n_cut, per_user_out, &d_rows));
+    CF_HIP(hipMemcpyAsync(d_users, users, (size_t)n * 4, hipMemcpyHostToDevice, e->stream));
+    int st = topk_device(e, d_users, n, k, exclude_train, d_mask, d_idx, nullptr);
+    if (st == CF_OK) st = metrics_device(e, d_users, n, d_idx, k, cutoffs, n_cut, d_rows);
+    if (st == CF_OK) st = eval_finish(e, n, n_cut, d_rows, sums_out, per_user_out);
+    if (st != CF_OK) {
+        (void)hipStreamSynchronize(e->stream);   // `users` may be local; the buffers above are freed on return
+        return st;
+    }
+    if (idx_out && idx_out != d_idx) CF_HIP(hipMemcpy(idx_out, d_idx, (size_t)n * k * 4, hipMemcpyDeviceToHost));
     return CF_OK;
 }
 

@@ -1,6 +1,6 @@
 // cf_kernels.h -- argument blocks shared by the host engine (cf_engine.cpp)
-// and the gfx950 kernels (cf_kernels.hip, cf_eval.hip).  Plain structs passed
-// by value as kernel arguments; no torch types anywhere.
+// and the gfx950 kernels (cf_kernels.hip, cf_eval.hip, cf_metrics.hip).  Plain
+// structs passed by value as kernel arguments; no torch types anywhere.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -386,6 +386,29 @@ struct TopkArgs {
     int32_t* __restrict__ idx_out;   // [n_users, k]
     float* __restrict__ val_out;     // [n_users, k]
 };
+
+// ranking metrics of device lists (cf_metrics.hip; cf_eval_lists / cf_evaluate)
+constexpr int kEvalN = 7;        // CF_EVAL_N: pre, recall, ndcg, map, mrr, hr, arhr
+constexpr int kEvalMaxCut = 8;
+constexpr int kEvalMaxK = 4096;  // the largest cutoff (entries of disc)
+struct MetricsArgs {
+    int64_t n;                   // users in this call
+    int64_t n_users;
+    int k;                       // row stride of idx
+    int n_cut;
+    int cutoffs[kEvalMaxCut];    // strictly ascending, 1 .. min(k, kEvalMaxK)
+    const int32_t* __restrict__ users;      // [n]
+    const int32_t* __restrict__ idx;        // [n, k], -1 pads
+    const int64_t* __restrict__ t_indptr;   // truth CSR, rows sorted
+    const int32_t* __restrict__ t_indices;
+    const double* __restrict__ disc;        // [kEvalMaxK] 1 / log2(p + 2)
+    double* __restrict__ per_user;          // [n, n_cut, kEvalN]
+    double* __restrict__ partial;           // [metrics_partials(n), n_cut * kEvalN]
+    double* __restrict__ sums;              // [n_cut, kEvalN]
+};
+int metrics_partials(int64_t n);
+// per-user rows, block partials, fold: three launches, sums in a fixed order
+hipError_t launch_metrics(const MetricsArgs& a, hipStream_t s);
 
 // ---- host launchers (cf_kernels.hip / cf_eval.hip) -------------------------
 hipError_t launch_prep(const StepArgs& a, hipStream_t s);   // sample/load + count

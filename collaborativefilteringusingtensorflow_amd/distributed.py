@@ -51,6 +51,22 @@ def local_csr(indptr, indices, u0, u1):
     return (indptr[u0:u1 + 1] - lo).astype(np.int64), np.asarray(indices[lo:hi], dtype=np.int32)
 
 
+def reduce_eval(sums, n, group=None):
+    """Combine per-rank device evaluations of disjoint user shards
+    (Engine.evaluate on each rank's own users): all-reduce (SUM, float64) of
+    the [n_cut, 7] metric sums and of the user count.  Returns (sums, n) of
+    the whole user set -- ranking.scores_from_sums turns them into scores."""
+    import torch
+    import torch.distributed as dist
+    a = np.asarray(sums, dtype=np.float64)
+    t = torch.cat([torch.from_numpy(a.reshape(-1).copy()), torch.tensor([float(n)], dtype=torch.float64)])
+    if dist.get_backend(group) != "gloo":   # RCCL reduces device tensors
+        t = t.cuda()
+    dist.all_reduce(t, op=dist.ReduceOp.SUM, group=group)
+    t = t.cpu().numpy()
+    return t[:-1].reshape(a.shape), int(round(float(t[-1])))
+
+
 def _gloo_dev(dist, t, group):
     """gloo stages device tensors through host copies (the collectives below
     are called on host copies and copied back)."""

@@ -501,6 +501,104 @@ class Engine(object):
                                       _ptr(idx, ctypes.c_int32), None), "cf_score_topk")
         return idx
 
+    # ---- device metrics (cf_set_truth / cf_eval_lists / cf_evaluate) ---------------
+    def set_truth(self, indptr, indices):
+        """The held-out (test) CSR over this engine's users, rows strictly
+        ascending; a user's LOOV truth is its row's first item."""
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        indices = _i32(indices)
+        if indptr.shape[0] != self.n_users + 1:
+            raise ValueError("indptr must have n_users + 1 entries")
+        N.check(self._L.cf_set_truth(self._h, ctypes.c_void_p(indptr.ctypes.data),
+                                     ctypes.c_void_p(indices.ctypes.data), int(indices.shape[0])),
+                "cf_set_truth")
+
+    @staticmethod
+    def _cutoffs(cutoffs):
+        c = _i32(np.atleast_1d(cutoffs)).reshape(-1)
+        return c, _ptr(c, ctypes.c_int32)
+
+    def eval_lists(self, users, idx, cutoffs, per_user=False):
+        """ranking.py's metrics of ready-made lists idx [n, k] (-1 pads) of
+        ``users`` at ``cutoffs`` (cf_eval_lists): sums float64 [n_cut, 7] in
+        ranking.DEVICE_COLUMNS order, and with ``per_user`` the rows
+        [n, n_cut, 7] (a device tensor when ``users`` is one)."""
+        cut, cp = self._cutoffs(cutoffs)
+        sums = np.zeros((cut.shape[0], 7), dtype=np.float64)
+        sp = _ptr(sums, ctypes.c_double)
+        k0 = max(int(cut[-1]), 1) if cut.shape[0] else 1   # the width of an empty call's lists
+        dev = _is_dev(users) or _is_dev(idx)
+        if dev:
+            import torch
+            where = users.device if _is_dev(users) else idx.device
+            users = users if _is_dev(users) else torch.as_tensor(_i32(users), device=where)
+            idx = idx if _is_dev(idx) else torch.as_tensor(_i32(idx), device=where)
+            u, up = _dev(users.reshape(-1), torch.int32, ctypes.c_int32)
+            n = u.shape[0]
+            ix, ip = _dev(idx.reshape(n, -1) if n else idx.reshape(0, k0), torch.int32,
+                          ctypes.c_int32)
+            rows = torch.empty((n, cut.shape[0], 7), dtype=torch.float64, device=where) if per_user else None
+            N.check(self._L.cf_eval_lists(self._h, ctypes.c_void_p(u.data_ptr()), n,
+                                          ctypes.c_void_p(ix.data_ptr()), int(ix.shape[1]), cp,
+                                          int(cut.shape[0]), sp,
+                                          ctypes.c_void_p(rows.data_ptr()) if per_user else None),
+                    "cf_eval_lists")
+            return (sums, rows) if per_user else sums
+        users = _i32(users).reshape(-1)
+        n = users.shape[0]
+        idx = _i32(idx)
+        idx = idx.reshape(n, -1) if n else idx.reshape(0, k0)
+        rows = np.empty((n, cut.shape[0], 7), dtype=np.float64) if per_user else None
+        N.check(self._L.cf_eval_lists(self._h, ctypes.c_void_p(users.ctypes.data), n,
+                                      ctypes.c_void_p(idx.ctypes.data), int(idx.shape[1]), cp,
+                                      int(cut.shape[0]), sp,
+                                      ctypes.c_void_p(rows.ctypes.data) if per_user else None),
+                "cf_eval_lists")
+        return (sums, rows) if per_user else sums
+
+    def evaluate(self, users, cutoffs, exclude_train=True, item_mask=None, per_user=False,
+                 return_lists=False):
+        """score_topk at k = the last cutoff and the metrics of its lists in
+        one call, the lists staying on the device (cf_evaluate).  Returns
+        sums [n_cut, 7], then the per-user rows and / or the lists when asked
+        (device tensors when ``users`` is one)."""
+        cut, cp = self._cutoffs(cutoffs)
+        k = int(cut[-1]) if cut.shape[0] else 0
+        sums = np.zeros((cut.shape[0], 7), dtype=np.float64)
+        sp = _ptr(sums, ctypes.c_double)
+        mp, mkeep = None, None
+        if item_mask is not None:
+            if _is_dev(item_mask):
+                import torch
+                mkeep, _ = _dev(item_mask.reshape(-1), torch.uint8, ctypes.c_uint8)
+                mp = ctypes.c_void_p(mkeep.data_ptr())
+            else:
+                mkeep = np.ascontiguousarray(item_mask, dtype=np.uint8).reshape(-1)
+                mp = ctypes.c_void_p(mkeep.ctypes.data)
+            if mkeep.shape[0] != self.n_items:
+                raise ValueError("item_mask must have n_items entries")
+        if _is_dev(users):
+            import torch
+            u, up = _dev(users.reshape(-1), torch.int32, ctypes.c_int32)
+            n = u.shape[0]
+            rows = torch.empty((n, cut.shape[0], 7), dtype=torch.float64, device=u.device) if per_user else None
+            lists = torch.empty((n, max(k, 0)), dtype=torch.int32, device=u.device) if return_lists else None
+            uptr = ctypes.c_void_p(u.data_ptr())
+            rp = ctypes.c_void_p(rows.data_ptr()) if per_user else None
+            lp = ctypes.c_void_p(lists.data_ptr()) if return_lists else None
+        else:
+            u = _i32(users).reshape(-1)
+            n = u.shape[0]
+            rows = np.empty((n, cut.shape[0], 7), dtype=np.float64) if per_user else None
+            lists = np.empty((n, max(k, 0)), dtype=np.int32) if return_lists else None
+            uptr = ctypes.c_void_p(u.ctypes.data)
+            rp = ctypes.c_void_p(rows.ctypes.data) if per_user else None
+            lp = ctypes.c_void_p(lists.ctypes.data) if return_lists else None
+        N.check(self._L.cf_evaluate(self._h, uptr, n, cp, int(cut.shape[0]), 1 if exclude_train else 0, mp,
+                                    sp, rp, lp), "cf_evaluate")
+        out = (sums,) + ((rows,) if per_user else ()) + ((lists,) if return_lists else ())
+        return out if len(out) > 1 else sums
+
     PATH_FLAGS = {"phased": 1, "pos_sort": 2, "item_records": 4, "deterministic": 8, "dense_items": 16,
                   "lds": 32, "sorted_batches": 64}
 

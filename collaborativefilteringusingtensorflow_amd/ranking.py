@@ -13,7 +13,8 @@ Pinned by tests/golden/ranking_cases.json (computed with the reference).
 import numpy as np
 
 __all__ = ["precision_k_score", "recall_k_score", "ndcg_k_score", "map_k_score",
-           "mrr_k_score", "hr_k_score", "arhr_k_score", "evaluateCV", "evaluateLOOV"]
+           "mrr_k_score", "hr_k_score", "arhr_k_score", "evaluateCV", "evaluateLOOV",
+           "DEVICE_COLUMNS", "scores_from_sums"]
 
 
 def _check(a, b, k, what="yss_true"):
@@ -109,3 +110,23 @@ def evaluateCV(yss_true, yss_pred, eval_metrics, k=5):
 
 def evaluateLOOV(ys_true, yss_pred, eval_metrics, k=5):
     return [_LOOV[m](ys_true, yss_pred, k) if m in _LOOV else None for m in eval_metrics]
+
+
+# columns of the device metric rows (include/cf_engine.h CF_EVAL_*)
+DEVICE_COLUMNS = ("pre", "recall", "ndcg", "map", "mrr", "hr", "arhr")
+
+
+def scores_from_sums(sums_row, n, eval_metrics, split_method):
+    """The list evaluateCV / evaluateLOOV would return, from one cutoff's row
+    of device sums over ``n`` users (Engine.evaluate / Engine.eval_lists):
+    the CV metrics are means, hr / arhr stay sums, unknown names give None."""
+    known = _CV if split_method == "cv" else _LOOV if split_method == "loov" else {}
+    out = []
+    for m in eval_metrics:
+        if m not in known:
+            out.append(None)
+        elif m in _CV:
+            out.append(float(sums_row[DEVICE_COLUMNS.index(m)]) / n)
+        else:
+            out.append(float(sums_row[DEVICE_COLUMNS.index(m)]))
+    return out

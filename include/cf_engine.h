@@ -101,7 +101,9 @@ enum cf_kernel_id {
                             a remote group member (cf_xchg_grad_part 2)      */
     CF_K_EPOCH_ORDER = 14,/* sorted batches: an epoch's pair order (inverse
                             bijection keys + radix sort by batch), once per epoch */
-    CF_K_COUNT = 15
+    CF_K_METRICS = 15,   /* ranking metrics of the device lists: hit labels +
+                            per-user values, block partials, fold            */
+    CF_K_COUNT = 16
 };
 
 /*
@@ -468,6 +470,62 @@ int cf_score_topk(cf_engine* eng, const int32_t* host_users, int32_t n,
 int cf_score_topk_ex(cf_engine* eng, const int32_t* host_users, int32_t n,
                      int32_t k, int32_t exclude_train, const uint8_t* item_mask,
                      int32_t* host_idx_out, float* host_val_out);
+
+/*
+ * Ranking metrics on the device.  The columns of every metric row, in the
+ * order of ranking.DEVICE_COLUMNS:
+ */
+enum { CF_EVAL_PRE = 0, CF_EVAL_RECALL = 1, CF_EVAL_NDCG = 2, CF_EVAL_MAP = 3, CF_EVAL_MRR = 4,
+       CF_EVAL_HR = 5, CF_EVAL_ARHR = 6, CF_EVAL_N = 7 };
+/*
+ * The held-out (test) matrix as CSR over the engine's own users, indexed as
+ * in cf_set_interactions; host or device memory.  Replaces
+ *   yss_true = [set(tstsR[u].nonzero()[1]) ...]       bprmf.py:117-120 (cv)
+ *   ys_true  = [tstsR[u].nonzero()[1][0] ...]          bprmf.py:121-123 (loov)
+ * -- a user's truth set is its row, its LOOV truth the row's first item.
+ * Rows must be strictly ascending with ids in [0, n_items); otherwise
+ * CF_EINVAL and nothing is copied.  The engine keeps its own device copy and
+ * the host row pointers; a second call replaces the first.
+ */
+int cf_set_truth(cf_engine* eng, const int64_t* indptr /*[n_users+1]*/, const int32_t* indices, int64_t nnz);
+/*
+ * The metrics of n ready-made lists idx [n, k] (-1 pads; e.g. cf_score_topk
+ * or cf_ens_score_topk output) of users [n] against the truth rows, at n_cut
+ * cutoffs (1..8 of them, strictly ascending, 1..4096, the last <= k): the
+ * per-user terms of src/metrics/ranking.py:11-120 with its definitions
+ * (precision_k_score :11-18, recall_k_score :20-27, ndcg_k_score :29-40 with
+ * the list's own sorted labels as the ideal and max(ideal, 1), map_k_score
+ * :43-56 over |truth|, mrr_k_score :58-72, hr_k_score :75-82, arhr_k_score
+ * :84-91), computed in fp64 in ranking.py's operation order,
+ * so every column but ndcg (libm's log2 against numpy's) is bit-identical
+ * to it.  An id repeated inside one list counts once per position, where
+ * precision_k_score's set counts it once: a top-k list never repeats.
+ * sums_out [n_cut, CF_EVAL_N] (host) = the sums over the n users, in a
+ * fixed order (no float atomics: two calls give the same bits) -- the
+ * reference's means are sums / n, its hr / arhr the sums themselves;
+ * per_user_out (NULL = skip) [n, n_cut, CF_EVAL_N].  users, idx and
+ * per_user_out may be host or device memory.  CF_ESTATE without a truth;
+ * CF_EINVAL for n < 0, bad cutoffs, a user id out of range or a user whose
+ * truth row is empty (map_k_score divides by len(truth)); nothing is computed
+ * then.  n == 0: zero sums.
+ */
+int cf_eval_lists(cf_engine* eng, const int32_t* users, int32_t n, const int32_t* idx /*[n,k], -1 pads*/, int32_t k,
+                  const int32_t* cutoffs, int32_t n_cut,
+                  double* sums_out /*[n_cut, CF_EVAL_N]*/, double* per_user_out_or_NULL /*[n, n_cut, CF_EVAL_N]*/);
+/*
+ * cf_score_topk_ex with k = the last cutoff (the same kernels, obeying
+ * "topk_path"), then cf_eval_lists on the lists where they sit: one epoch's
+ *   yss_pred = self.__recommend(...); scores = evaluateCV / evaluateLOOV(...)
+ *   bprmf.py:152-153 over ranking.py:11-120
+ * without the lists leaving the device.  idx_out_or_NULL [n, last cutoff]
+ * receives the lists (host or device).  With host users and both optional
+ * outputs NULL the only device-to-host transfer is sums_out.  Errors as
+ * cf_eval_lists and cf_score_topk_ex (exclude_train without interactions:
+ * CF_ESTATE).
+ */
+int cf_evaluate(cf_engine* eng, const int32_t* users, int32_t n, const int32_t* cutoffs, int32_t n_cut,
+                int32_t exclude_train, const uint8_t* item_mask,
+                double* sums_out, double* per_user_out_or_NULL, int32_t* idx_out_or_NULL /*[n, cutoffs[n_cut-1]]*/);
 
 /*
  * Engine options (name, value):
