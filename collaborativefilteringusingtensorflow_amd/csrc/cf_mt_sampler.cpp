@@ -6,6 +6,7 @@
 //   src/samplers/sampler_ranking.py:22-37      (kind 0)
 //   src/samplers/sampler_uij_ranking.py:22-38  (kind 1, W = 1)
 //   src/samplers/sampler_gbpr.py:23-43         (kind 2)
+//   src/samplers/sampler_lrml_ranking.py:20-35 (kind 3)
 // on its producer side, by restating the algorithms of numpy's legacy
 // RandomState (numpy/random/mtrand.pyx + src/mt19937, src/distributions):
 //   * seed(s), s < 2^32: MT19937 init_genrand(s);
@@ -17,7 +18,9 @@
 //     index the list.
 // Stream order per batch: negatives randint (B, W); GBPR: the discarded
 // group randint (B, G); then per pair, per negative, the rejection redraws,
-// then (GBPR) the group choice.  Epochs re-shuffle the already shuffled pair
+// then (GBPR) the group choice.  Kind 3 draws nothing per batch up front: per
+// row, randint(0, n_users, 1)[0] then randint(0, n_items, 1)[0], both redrawn
+// while the pair is a train interaction.  Epochs re-shuffle the already shuffled pair
 // array (np.random.shuffle in place, sampler_ranking.py:24) and yield
 // floor(nnz / B) batches.  The consumer-side last-batch race of the
 // reference's queue is not reproduced: this is the stream the
@@ -153,9 +156,11 @@ extern "C" {
 int cf_mt_sampler_create(const int64_t* indptr, const int32_t* indices, int64_t n_users,
                          int64_t n_items, int32_t kind, int32_t n_neg, int32_t gsize,
                          int32_t batch_size, uint32_t seed, cf_mt_sampler** out) {
-    if (!out || !indptr || n_users < 1 || n_items < 1 || kind < 0 || kind > 2 || batch_size < 1)
+    if (!out || !indptr || n_users < 1 || n_items < 1 || kind < 0 || kind > 3 || batch_size < 1)
         return cfi::set_error(CF_EINVAL, "bad arguments");
     if (kind == 1) n_neg = 1;
+    if (kind == 3 && (n_neg != 1 || gsize != 0))
+        return cfi::set_error(CF_EINVAL, "the LRML sampler (kind 3) takes n_neg 1 and gsize 0");
     if (n_neg < 1 || (kind == 2 && gsize < 1)) return cfi::set_error(CF_EINVAL, "bad n_neg / gsize");
     const int64_t nnz = indptr[n_users];
     if (nnz < 1 || !indices) return cfi::set_error(CF_EINVAL, "no interactions");
@@ -214,6 +219,19 @@ int cf_mt_sampler_next(cf_mt_sampler* s, int32_t* pairs, int32_t* negs, int32_t*
     const int B = s->B, W = s->W, G = s->G;
     const int32_t* src = s->pairs.data() + (size_t)(2 * s->batch * (int64_t)B);
     std::memcpy(pairs, src, (size_t)B * 2 * sizeof(int32_t));
+    if (s->kind == 3) {  // sampler_lrml_ranking.py:29-33: negs is [B, 2] (user, item)
+        for (int p = 0; p < B; ++p) {
+            int64_t u, i;
+            do {
+                u = randint(s->g, 0, s->n_users);
+                i = randint(s->g, 0, s->n_items);
+            } while (s->positive(u, i));  // while self.trasR[u,i]>0
+            negs[2 * p] = (int32_t)u;
+            negs[2 * p + 1] = (int32_t)i;
+        }
+        s->batch += 1;
+        return CF_OK;
+    }
     // negItems_batch = np.random.randint(0, n_items, size=(B, W))
     for (int64_t k = 0; k < (int64_t)B * W; ++k) negs[k] = (int32_t)randint(s->g, 0, s->n_items);
     // sampler_gbpr.py:34 draws a (B, G) block of users it later overwrites

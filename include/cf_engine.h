@@ -697,7 +697,11 @@ int cf_ratings_free(cf_ratings* r);
  * before the sampler is built (sampler_ranking.py:22-37 kind 0,
  * sampler_uij_ranking.py:22-38 kind 1, sampler_gbpr.py:23-43 kind 2):
  * numpy's legacy MT19937 RandomState shuffle / randint / choice restated
- * (csrc/cf_mt_sampler.cpp).  Host batches, fed with cf_step. */
+ * (csrc/cf_mt_sampler.cpp).  Host batches, fed with cf_step.
+ * Kind 3 is sampler_lrml_ranking.py:20-35 (n_neg 1, gsize 0): pairs [B,2] =
+ * the positive pairs, negs [B,2] = the negative (user, item) pairs, each
+ * drawn as randint(0, n_users, 1)[0] then randint(0, n_items, 1)[0] and both
+ * redrawn while the pair is a train interaction; fed with cf_lrml_step. */
 typedef struct cf_mt_sampler cf_mt_sampler;
 int cf_mt_sampler_create(const int64_t* indptr, const int32_t* indices, int64_t n_users,
                          int64_t n_items, int32_t kind, int32_t n_neg, int32_t gsize,
@@ -756,6 +760,45 @@ int cf_ens_step_w(cf_ensemble* e, const int32_t* host_pairs, const int32_t* host
 int cf_ens_take_loss(cf_ensemble* e, double* sum_out);
 int cf_ens_score_topk(cf_ensemble* e, const int32_t* host_users, int32_t n, int32_t k,
                       int32_t exclude_train, int32_t* host_idx_out, float* host_val_out);
+
+/* ---- LRML: latent relational metric learning ---------------------------------
+ * src/models/others/models/lrml.py: U[n_users,d], V[n_items,d] trained with
+ * sparse Adagrad (TF1 sums duplicate rows first) on batches of B positive
+ * pairs and B negative pairs from sampler_lrml_ranking; Key[d,M] and Mem[M,d]
+ * are drawn once and never trained (lrml.py:114 var_list); all four
+ * random-normal, not truncated (lrml.py:30-41).  Per row (lrml.py:59-80):
+ * e = U_u o V_i, a = softmax(e^T Key), r = a^T Mem, loss = sum relu(
+ * |U_u + r - V_i|^2 + margin - |U_u' + r - V_i'|^2); after the update every
+ * row of U and V is clipped to norm <= clip_norm (lrml.py:106-116).  Limits:
+ * d 1..128, M 1..64 (Key^T and Mem live in LDS).  Tables for get/set: 0 U,
+ * 1 V, 2 Key, 3 Mem, 4 AU, 5 AV (the Adagrad accumulators); sizes in floats.
+ * The lr decay of lrml.py:197 is cosmetic (the optimizer keeps the initial lr). */
+typedef struct cf_lrml cf_lrml;
+/* cf_lrml_score_topk predict_mode */
+enum {
+    CF_LRML_REFERENCE = 0,   /* lrml.py:86-104 as written: elementwise product with
+                                Key^T, softmax over the factor axis per memory slot */
+    CF_LRML_TRAIN = 1        /* the training attention of lrml.py:72-74 (not a parity target) */
+};
+int cf_lrml_create(int64_t n_users, int64_t n_items, int32_t d, int32_t M, float margin,
+                   float clip_norm, float lr, float acc_init, int32_t device, cf_lrml** out);
+int cf_lrml_destroy(cf_lrml* e);
+int cf_lrml_init_params(cf_lrml* e, float mean, float stddev, uint64_t seed);
+int cf_lrml_set_table(cf_lrml* e, int32_t table, const float* host_src, int64_t n);
+int cf_lrml_get_table(cf_lrml* e, int32_t table, float* host_dst, int64_t n);
+int cf_lrml_set_interactions(cf_lrml* e, const int64_t* indptr, const int32_t* indices, int64_t nnz);
+/* one optimizer step on B host positive pairs [B,2] and B host negative pairs
+ * [B,2] (user, item) int32, range-checked before any launch; loss_out (may be
+ * NULL, else syncs) = the pre-update loss of the batch (lrml.py:79) */
+int cf_lrml_step(cf_lrml* e, const int32_t* host_pos, const int32_t* host_neg, int32_t B,
+                 double* loss_out);
+/* sum of the step losses since the last call (syncs), then reset */
+int cf_lrml_take_loss(cf_lrml* e, double* sum_out);
+/* top-k of the predict scores (lrml.py:86-104, 126) with the exclude / tie
+ * rules of cf_score_topk */
+int cf_lrml_score_topk(cf_lrml* e, const int32_t* host_users, int32_t n, int32_t k,
+                       int32_t exclude_train, int32_t predict_mode, int32_t* host_idx_out,
+                       float* host_val_out);
 
 /* ---- synthetic implicit-feedback graphs (bench configs) --------- */
 /*
