@@ -17,6 +17,7 @@ CF_AMF_REFERENCE, CF_AMF_APR = 0, 1
 AMF_MODES = {"reference": CF_AMF_REFERENCE, "apr": CF_AMF_APR}
 CF_LRML_REFERENCE, CF_LRML_TRAIN = 0, 1
 LRML_MODES = {"reference": CF_LRML_REFERENCE, "train": CF_LRML_TRAIN}
+CF_PW_MF, CF_PW_SVD = 0, 1
 MODEL_IDS = {"bpr": CF_BPR, "bprmf": CF_BPR, "gbpr": CF_GBPR, "gbprmf": CF_GBPR,
              "cml": CF_CML, "amf": CF_AMF, "plr": CF_PLR, "prigp": CF_PLR, "cplr": CF_PLR}
 TABLES = {"user": 0, "item": 1, "bias": 2, "acc_user": 3, "acc_item": 4, "acc_bias": 5}
@@ -164,6 +165,21 @@ SIGNATURES = {
     "cf_lrml_step": (ctypes.c_int, [_P, _PI32, _PI32, _I32, _PD]),
     "cf_lrml_take_loss": (ctypes.c_int, [_P, _PD]),
     "cf_lrml_score_topk": (ctypes.c_int, [_P, _PI32, _I32, _I32, _I32, _I32, _PI32, _PF]),
+    "cf_pw_create": (ctypes.c_int, [_I64, _I64, _I32, _I32, _F, _F, _F, _F, _I32, ctypes.POINTER(_P)]),
+    "cf_pw_destroy": (ctypes.c_int, [_P]),
+    "cf_pw_init_params": (ctypes.c_int, [_P, _F, _F, _I32, _U64]),
+    "cf_pw_set_table": (ctypes.c_int, [_P, _I32, _PF, _I64]),
+    "cf_pw_get_table": (ctypes.c_int, [_P, _I32, _PF, _I64]),
+    "cf_pw_set_interactions": (ctypes.c_int, [_P, _PI64, _PI32, _I64]),
+    "cf_pw_step": (ctypes.c_int, [_P, _PI32, _PF, _I32, _PD]),
+    "cf_pw_take_loss": (ctypes.c_int, [_P, _PD]),
+    "cf_pw_eval": (ctypes.c_int, [_P, _PI32, _PF, _I64, _F, _F, _PF, _PD]),
+    "cf_pw_score_topk": (ctypes.c_int, [_P, _PI32, _I32, _I32, _I32, _PI32, _PF]),
+    "cf_rating_sampler_create": (ctypes.c_int, [_PI64, _PI32, _PD, _I64, _I64, ctypes.c_double, _I32,
+                                                 ctypes.c_uint32, ctypes.POINTER(_P)]),
+    "cf_rating_sampler_next": (ctypes.c_int, [_P, _PI32, _PF]),
+    "cf_rating_sampler_state": (ctypes.c_int, [_P, _PI64, _PI64]),
+    "cf_rating_sampler_free": (ctypes.c_int, [_P]),
     "cf_synth_degrees": (ctypes.c_int, [_I64, ctypes.c_double, _U64, _I64, _I64, _PI64]),
     "cf_synth_items": (ctypes.c_int, [_I64, ctypes.c_double, _U64, _I64, _I64, _PI64, _PI32, _I32]),
     "cf_synth_item_users": (ctypes.c_int, [_I64, _I64, ctypes.c_double, ctypes.c_double, _U64, _PI64,

@@ -475,3 +475,128 @@ int cf_tuple_sampler_free(cf_tuple_sampler* s) {
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------------------
+// sampler_rating (src/samplers/sampler_rating.py:22-39), the feed of MF, SVD
+// and WRMF: the (user, item, rating) tuples in trasR.nonzero() order, never
+// shuffled as a whole.  Batch k is rows [kB, (k+1)B).  With num_neg =
+// int(B * negRatio) == 0 the batch is a view of the tuple array and
+// np.random.shuffle(batch) permutes the slice in place: the order persists
+// into the next epoch, the sets never change, the trailing nnz % B tuples are
+// never emitted.  With num_neg > 0, per negative: user = randint(0, n_users),
+// item = randint(0, n_items), the item alone redrawn while it is in
+// Pos(user); the rows (user, item, 0) are concatenated (a copy) and the
+// B + num_neg rows shuffled.  shuffle is the 2-D row swap restated above.
+// ---------------------------------------------------------------------------
+struct cf_rating_sampler {
+    int64_t n_users = 0, n_items = 0;
+    int B = 1, n_neg = 0;
+    std::vector<int64_t> indptr;
+    std::vector<int32_t> indices;
+    std::vector<int32_t> ui;      // [nnz, 2]
+    std::vector<float> r;         // [nnz]
+    int64_t nnz = 0, per_epoch = 0, batch = 0, epoch = 0;
+    MT19937 g;
+};
+
+extern "C" {
+
+int cf_rating_sampler_create(const int64_t* indptr, const int32_t* indices, const double* values,
+                             int64_t n_users, int64_t n_items, double neg_ratio, int32_t batch_size,
+                             uint32_t seed, cf_rating_sampler** out) {
+    if (!out || !indptr || !indices || !values || n_users < 1 || n_items < 1 || batch_size < 1 ||
+        !(neg_ratio >= 0.0) || !std::isfinite(neg_ratio) || neg_ratio * batch_size > (double)(1 << 24))
+        return cfi::set_error(CF_EINVAL, "bad arguments");
+    if (indptr[0] != 0) return cfi::set_error(CF_EINVAL, "indptr must start at 0");
+    const int64_t nnz = indptr[n_users];
+    if (nnz < 1) return cfi::set_error(CF_EINVAL, "no interactions");
+    if (batch_size > nnz) return cfi::set_error(CF_EINVAL, "batch size exceeds the number of interactions");
+    const int n_neg = (int)(batch_size * neg_ratio);   // int(self.batch_size*self.negRatio), sampler_rating.py:29
+    for (int64_t u = 0; u < n_users; ++u) {
+        if (indptr[u + 1] < indptr[u]) return cfi::set_error(CF_EINVAL, "indptr not monotone");
+        if (n_neg > 0 && indptr[u + 1] - indptr[u] >= n_items)
+            return cfi::set_error(CF_EINVAL, "a user has every item as a positive");
+        for (int64_t k = indptr[u]; k < indptr[u + 1]; ++k) {
+            if (indices[k] < 0 || indices[k] >= n_items) return cfi::set_error(CF_EINVAL, "item id out of range");
+            if (k > indptr[u] && indices[k - 1] >= indices[k])
+                return cfi::set_error(CF_EINVAL, "CSR rows must be sorted, unique");
+            if (!std::isfinite(values[k])) return cfi::set_error(CF_EINVAL, "a rating is not finite");
+        }
+    }
+    cf_rating_sampler* s = new cf_rating_sampler();
+    s->n_users = n_users;
+    s->n_items = n_items;
+    s->B = batch_size;
+    s->n_neg = n_neg;
+    s->nnz = nnz;
+    s->per_epoch = nnz / batch_size;   // int(len(tuples) / batch_size), sampler_rating.py:24
+    s->indptr.assign(indptr, indptr + n_users + 1);
+    s->indices.assign(indices, indices + nnz);
+    s->ui.resize((size_t)(2 * nnz));
+    s->r.resize((size_t)nnz);
+    for (int64_t u = 0; u < n_users; ++u)
+        for (int64_t k = indptr[u]; k < indptr[u + 1]; ++k) {
+            s->ui[(size_t)(2 * k)] = (int32_t)u;
+            s->ui[(size_t)(2 * k + 1)] = indices[k];
+            s->r[(size_t)k] = (float)values[k];
+        }
+    s->g.seed(seed);
+    *out = s;
+    return CF_OK;
+}
+
+int cf_rating_sampler_next(cf_rating_sampler* s, int32_t* ui, float* r) {
+    if (!s || !ui || !r) return cfi::set_error(CF_EINVAL, "bad arguments");
+    if (s->batch >= s->per_epoch) {   // the for loop of sampler_rating.py:24 starts over: no shuffle
+        s->batch = 0;
+        s->epoch += 1;
+    }
+    const int B = s->B, n = B + s->n_neg;
+    int32_t* src_ui = s->ui.data() + (size_t)(2 * s->batch * (int64_t)B);
+    float* src_r = s->r.data() + (size_t)(s->batch * (int64_t)B);
+    int32_t* x_ui = src_ui;   // num_neg == 0: the view itself is shuffled
+    float* x_r = src_r;
+    if (s->n_neg > 0) {
+        std::memcpy(ui, src_ui, (size_t)B * 2 * sizeof(int32_t));
+        std::memcpy(r, src_r, (size_t)B * sizeof(float));
+        for (int q = B; q < n; ++q) {
+            const int64_t u = randint(s->g, 0, s->n_users);
+            int64_t i = randint(s->g, 0, s->n_items);
+            const int32_t* b = s->indices.data() + s->indptr[(size_t)u];
+            const int32_t* e = s->indices.data() + s->indptr[(size_t)u + 1];
+            while (std::binary_search(b, e, (int32_t)i)) i = randint(s->g, 0, s->n_items);
+            ui[2 * q] = (int32_t)u;
+            ui[2 * q + 1] = (int32_t)i;
+            r[q] = 0.f;
+        }
+        x_ui = ui;
+        x_r = r;
+    }
+    for (int64_t i = n - 1; i >= 1; --i) {   // np.random.shuffle(batch): rows i and j swap
+        const int64_t j = (int64_t)random_interval(s->g, (uint64_t)i);
+        if (i == j) continue;
+        std::swap(x_ui[2 * i], x_ui[2 * j]);
+        std::swap(x_ui[2 * i + 1], x_ui[2 * j + 1]);
+        std::swap(x_r[i], x_r[j]);
+    }
+    if (s->n_neg == 0) {
+        std::memcpy(ui, src_ui, (size_t)B * 2 * sizeof(int32_t));
+        std::memcpy(r, src_r, (size_t)B * sizeof(float));
+    }
+    s->batch += 1;
+    return CF_OK;
+}
+
+int cf_rating_sampler_state(const cf_rating_sampler* s, int64_t* epoch_out, int64_t* batch_out) {
+    if (!s) return cfi::set_error(CF_EINVAL, "null sampler");
+    if (epoch_out) *epoch_out = s->batch >= s->per_epoch ? s->epoch + 1 : s->epoch;
+    if (batch_out) *batch_out = s->batch >= s->per_epoch ? 0 : s->batch;
+    return CF_OK;
+}
+
+int cf_rating_sampler_free(cf_rating_sampler* s) {
+    delete s;
+    return CF_OK;
+}
+
+}  // extern "C"

@@ -800,6 +800,70 @@ int cf_lrml_score_topk(cf_lrml* e, const int32_t* host_users, int32_t n, int32_t
                        int32_t exclude_train, int32_t predict_mode, int32_t* host_idx_out,
                        float* host_val_out);
 
+/* ---- the pointwise family: MF, SVD, WRMF --------------------------------------
+ * src/models/basic/models/mf.py, svd.py, wrmf.py, fed by sampler_rating:
+ * U[n_users,d], V[n_items,d] (SVD: and the kernel matrix K[d,d], svd.py:29-31),
+ * all truncated-normal.  Per batch row (u, i, r): pred = <U_u, V_i> (mf.py:62-68,
+ * wrmf.py:69-75) or <U_u K, V_i> (svd.py:65-71), e = pred - r, loss =
+ * 1/2 sum (e s)^2 + reg 1/2 (sum |U_u|^2 + sum |V_i|^2) with s =
+ * float32(sqrt(weight)) (wrmf.py:59-60: every row weighted alike; MF and SVD:
+ * weight 1; K is not regularised, svd.py:51-54).  tf.train.AdagradOptimizer:
+ * duplicate U / V rows are summed first, then one update per distinct row; K's
+ * gradient is dense, every element is updated every step.  WRMF is kind
+ * CF_PW_MF with weight != 1.  Limits: d 1..128.  Tables for get/set: 0 U, 1 V,
+ * 2 K, 3 AU, 4 AV, 5 AK (the Adagrad accumulators; K / AK: SVD only, CF_EINVAL
+ * otherwise); sizes in floats.  The lr decay of mf.py:111 is cosmetic (the
+ * optimizer keeps the initial lr).  No sum uses float atomics: equal tables and
+ * batches give equal bits. */
+typedef struct cf_pw cf_pw;
+enum {
+    CF_PW_MF = 0,    /* mf.py, and wrmf.py through weight */
+    CF_PW_SVD = 1    /* svd.py */
+};
+int cf_pw_create(int64_t n_users, int64_t n_items, int32_t d, int32_t kind, float weight, float reg,
+                 float lr, float acc_init, int32_t device, cf_pw** out);
+int cf_pw_destroy(cf_pw* e);
+int cf_pw_init_params(cf_pw* e, float mean, float stddev, int32_t truncated, uint64_t seed);
+int cf_pw_set_table(cf_pw* e, int32_t table, const float* host_src, int64_t n);
+int cf_pw_get_table(cf_pw* e, int32_t table, float* host_dst, int64_t n);
+/* the train CSR (sorted rows) behind exclude_train of cf_pw_score_topk */
+int cf_pw_set_interactions(cf_pw* e, const int64_t* indptr, const int32_t* indices, int64_t nnz);
+/* one optimizer step on B host rows: host_ui [B,2] (user, item) int32, host_r
+ * [B] ratings; ids are range-checked and ratings checked finite before any
+ * launch (CF_EINVAL, tables untouched); loss_out (may be NULL, else syncs) =
+ * the pre-update loss of the batch (mf.py:57-59) */
+int cf_pw_step(cf_pw* e, const int32_t* host_ui, const float* host_r, int32_t B, double* loss_out);
+/* sum of the step losses since the last call (syncs), then reset */
+int cf_pw_take_loss(cf_pw* e, double* sum_out);
+/* mf.py:77-80 / svd.py:80-83 on n host tuples: pred = clip_by_value(predict,
+ * lo, hi) into host_pred_out (NULL: not returned); sums_out[0] = sum |r - pred|,
+ * sums_out[1] = sum (r - pred)^2, in fp64 from the float32 predictions, added
+ * in a fixed order (metrics/rating.py:4-16 divide them by n) */
+int cf_pw_eval(cf_pw* e, const int32_t* host_ui, const float* host_r, int64_t n, float lo, float hi,
+               float* host_pred_out, double* sums_out);
+/* wrmf.py:78-81, 98-111: top-k of U[users] V^T with the exclude / tie rules of
+ * cf_score_topk; CF_PW_MF only (svd.py has no recommend: CF_EINVAL) */
+int cf_pw_score_topk(cf_pw* e, const int32_t* host_users, int32_t n, int32_t k, int32_t exclude_train,
+                     int32_t* host_idx_out, float* host_val_out);
+
+/* ---- sampler_rating, bit-exact (host) ------------------------------------------
+ * src/samplers/sampler_rating.py:22-39 for np.random.seed(seed) set right
+ * before the sampler is built: the (user, item, rating) tuples in nonzero()
+ * order; batch k of an epoch is rows [kB, (k+1)B), int(nnz / B) batches, the
+ * epoch is never shuffled.  n_neg = int(B * neg_ratio): 0 -> the slice itself
+ * is shuffled in place (the order persists into later epochs, the trailing
+ * nnz % B tuples are never emitted); > 0 -> per negative user = randint(0,
+ * n_users), item = randint(0, n_items), the item alone redrawn while it is a
+ * train item of the user, rows (user, item, 0) appended and the B + n_neg rows
+ * shuffled.  next fills ui [B + n_neg, 2] and r [B + n_neg]. */
+typedef struct cf_rating_sampler cf_rating_sampler;
+int cf_rating_sampler_create(const int64_t* indptr, const int32_t* indices, const double* values,
+                             int64_t n_users, int64_t n_items, double neg_ratio, int32_t batch_size,
+                             uint32_t seed, cf_rating_sampler** out);
+int cf_rating_sampler_next(cf_rating_sampler* s, int32_t* ui, float* r);
+int cf_rating_sampler_state(const cf_rating_sampler* s, int64_t* epoch_out, int64_t* batch_out);
+int cf_rating_sampler_free(cf_rating_sampler* s);
+
 /* ---- synthetic implicit-feedback graphs (bench configs) --------- */
 /*
  * Users [u_begin, u_end) of a graph with per-user degree 1 + Poisson(mean-1)
