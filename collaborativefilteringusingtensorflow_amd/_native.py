@@ -7,6 +7,8 @@ import ctypes
 import os
 import re
 
+import numpy as np
+
 _PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("CF_ENGINE_LIB", os.path.join(_PKG, "build", "libcf_engine.so"))
 HEADER_PATH = os.path.join(os.path.dirname(_PKG), "include", "cf_engine.h")
@@ -248,3 +250,68 @@ def device_count():
     n = ctypes.c_int32(0)
     lib().cf_device_count(ctypes.byref(n))
     return int(n.value)
+
+
+def _ptr(a, ctype):
+    return a.ctypes.data_as(ctypes.POINTER(ctype))
+
+
+class _NativeObject(object):
+    """What the wrappers of the ensemble, LRML and pointwise objects share.  A
+    subclass sets ``PREFIX`` (the C prefix, "cf_ens") and ``TABLES``, gives
+    ``_shape(name)`` and creates the handle with ``_create``."""
+
+    PREFIX = None
+    TABLES = None
+
+    def _fn(self, name):
+        return getattr(self._L, "%s_%s" % (self.PREFIX, name))
+
+    def _call(self, name, *args):
+        check(self._fn(name)(self._h, *args), "%s_%s" % (self.PREFIX, name))
+
+    def _create(self, *args):
+        self._L = lib()
+        self._h = ctypes.c_void_p()
+        check(self._fn("create")(*(args + (ctypes.byref(self._h),))), self.PREFIX + "_create")
+
+    def close(self):
+        if getattr(self, "_h", None) and self._h.value:
+            self._fn("destroy")(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def set_table(self, name, arr):
+        a = np.ascontiguousarray(arr, dtype=np.float32)
+        if a.shape != self._shape(name):
+            raise ValueError("%s must be %s, got %s" % (name, self._shape(name), a.shape))
+        self._call("set_table", self.TABLES[name], _ptr(a, ctypes.c_float), a.size)
+
+    def get_table(self, name):
+        a = np.empty(self._shape(name), dtype=np.float32)
+        self._call("get_table", self.TABLES[name], _ptr(a, ctypes.c_float), a.size)
+        return a
+
+    def set_interactions(self, indptr, indices):
+        ip = np.ascontiguousarray(indptr, dtype=np.int64)
+        ix = np.ascontiguousarray(indices, dtype=np.int32)
+        self._call("set_interactions", _ptr(ip, ctypes.c_int64), _ptr(ix, ctypes.c_int32), ix.shape[0])
+
+    def take_loss(self):
+        s = ctypes.c_double(0.0)
+        self._call("take_loss", ctypes.byref(s))
+        return float(s.value)
+
+    def _score_topk(self, users, k, exclude_train, return_values, *extra):
+        """``extra``: the object's own arguments between exclude_train and the outputs."""
+        u = np.ascontiguousarray(users, dtype=np.int32)
+        idx = np.empty((u.shape[0], int(k)), dtype=np.int32)
+        val = np.empty((u.shape[0], int(k)), dtype=np.float32) if return_values else None
+        self._call("score_topk", _ptr(u, ctypes.c_int32), u.shape[0], int(k), int(bool(exclude_train)),
+                   *(extra + (_ptr(idx, ctypes.c_int32), _ptr(val, ctypes.c_float) if val is not None else None)))
+        return (idx, val) if return_values else idx

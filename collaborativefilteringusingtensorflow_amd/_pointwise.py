@@ -7,15 +7,12 @@ import time
 import numpy as np
 
 from . import _native as N
+from ._native import _ptr
 from ._model import parse_device
 from .rating import scores_from_sums
 
 TABLES = {"user": 0, "item": 1, "kernel": 2, "acc_user": 3, "acc_item": 4, "acc_kernel": 5}
 KINDS = {"mf": N.CF_PW_MF, "wrmf": N.CF_PW_MF, "svd": N.CF_PW_SVD}
-
-
-def _ptr(a, ctype):
-    return a.ctypes.data_as(ctypes.POINTER(ctype))
 
 
 def split_batch(batch):
@@ -26,32 +23,20 @@ def split_batch(batch):
     return np.ascontiguousarray(b[:, :2], dtype=np.int32), np.ascontiguousarray(b[:, 2], dtype=np.float32)
 
 
-class PointwiseEngine(object):
+class PointwiseEngine(N._NativeObject):
     """One HIP device's tables U [n_users, d], V [n_items, d] (``kind="svd"``:
     and the kernel matrix K [d, d]) with their Adagrad accumulators."""
+
+    PREFIX, TABLES = "cf_pw", TABLES
 
     def __init__(self, n_users, n_items, n_factors=10, kind="mf", weight=1.0, reg=0.02, lr=0.1,
                  acc_init=0.1, device=0):
         if kind not in KINDS:
             raise ValueError("kind must be one of %s" % sorted(KINDS))
-        L = N.lib()
-        self._L = L
         self.n_users, self.n_items, self.d = int(n_users), int(n_items), int(n_factors)
         self.kind = kind
-        self._h = ctypes.c_void_p()
-        N.check(L.cf_pw_create(self.n_users, self.n_items, self.d, KINDS[kind], float(weight), float(reg),
-                               float(lr), float(acc_init), int(device), ctypes.byref(self._h)), "cf_pw_create")
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._L.cf_pw_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(self.n_users, self.n_items, self.d, KINDS[kind], float(weight), float(reg), float(lr),
+                     float(acc_init), int(device))
 
     def _shape(self, name):
         return {"user": (self.n_users, self.d), "item": (self.n_items, self.d), "kernel": (self.d, self.d),
@@ -62,23 +47,6 @@ class PointwiseEngine(object):
         N.check(self._L.cf_pw_init_params(self._h, float(mean), float(stddev), int(bool(truncated)),
                                           int(seed) & 0xFFFFFFFFFFFFFFFF), "cf_pw_init_params")
 
-    def set_table(self, name, arr):
-        a = np.ascontiguousarray(arr, dtype=np.float32)
-        if a.shape != self._shape(name):
-            raise ValueError("%s must be %s, got %s" % (name, self._shape(name), a.shape))
-        N.check(self._L.cf_pw_set_table(self._h, TABLES[name], _ptr(a, ctypes.c_float), a.size), "cf_pw_set_table")
-
-    def get_table(self, name):
-        a = np.empty(self._shape(name), dtype=np.float32)
-        N.check(self._L.cf_pw_get_table(self._h, TABLES[name], _ptr(a, ctypes.c_float), a.size), "cf_pw_get_table")
-        return a
-
-    def set_interactions(self, indptr, indices):
-        ip = np.ascontiguousarray(indptr, dtype=np.int64)
-        ix = np.ascontiguousarray(indices, dtype=np.int32)
-        N.check(self._L.cf_pw_set_interactions(self._h, _ptr(ip, ctypes.c_int64), _ptr(ix, ctypes.c_int32),
-                                               ix.shape[0]), "cf_pw_set_interactions")
-
     def step(self, ui, r, return_loss=True):
         p = np.ascontiguousarray(ui, dtype=np.int32)
         q = np.ascontiguousarray(r, dtype=np.float32)
@@ -88,11 +56,6 @@ class PointwiseEngine(object):
         N.check(self._L.cf_pw_step(self._h, _ptr(p, ctypes.c_int32), _ptr(q, ctypes.c_float), p.shape[0],
                                    ctypes.byref(loss) if return_loss else None), "cf_pw_step")
         return float(loss.value) if return_loss else None
-
-    def take_loss(self):
-        s = ctypes.c_double(0.0)
-        N.check(self._L.cf_pw_take_loss(self._h, ctypes.byref(s)), "cf_pw_take_loss")
-        return float(s.value)
 
     def eval(self, ui, r, lo, hi, return_pred=True):
         """(pred float32 [n] or None, sum |r - pred|, sum (r - pred)^2)."""
@@ -108,14 +71,7 @@ class PointwiseEngine(object):
         return pred, float(sums[0]), float(sums[1])
 
     def score_topk(self, users, k, exclude_train=True, return_values=False):
-        u = np.ascontiguousarray(users, dtype=np.int32)
-        idx = np.empty((u.shape[0], int(k)), dtype=np.int32)
-        val = np.empty((u.shape[0], int(k)), dtype=np.float32) if return_values else None
-        N.check(self._L.cf_pw_score_topk(self._h, _ptr(u, ctypes.c_int32), u.shape[0], int(k),
-                                         int(bool(exclude_train)), _ptr(idx, ctypes.c_int32),
-                                         _ptr(val, ctypes.c_float) if val is not None else None),
-                "cf_pw_score_topk")
-        return (idx, val) if return_values else idx
+        return self._score_topk(users, k, exclude_train, return_values)
 
 
 class RatingModel(object):

@@ -24,7 +24,8 @@ SOURCES = ["cf_grad_bpr.hip", "cf_grad_amf.hip", "cf_grad_cml.hip", "cf_grad_gbp
            "cf_kernels.hip", "cf_eval.hip", "cf_metrics.hip", "cf_engine.cpp", "cf_synth.cpp", "cf_ingest.cpp",
            "cf_mt_sampler.cpp", "cf_ensemble.hip", "cf_det.hip", "cf_epoch.hip", "cf_lrml.hip",
            "cf_pointwise.hip"]
-HEADERS = ["cf_kernels.h", "cf_device.h", "cf_kernels_impl.h", os.path.join(ROOT, "include", "cf_engine.h")]
+HEADERS = ["cf_kernels.h", "cf_device.h", "cf_kernels_impl.h", "cf_host.h",
+           os.path.join(ROOT, "include", "cf_engine.h")]
 ARCH = os.environ.get("CF_OFFLOAD_ARCH", "gfx950")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["-O3", "-std=c++17", "-fPIC", "--offload-arch=" + ARCH, "-munsafe-fp-atomics",

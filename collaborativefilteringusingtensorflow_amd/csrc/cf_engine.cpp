@@ -14,78 +14,25 @@
 #include <vector>
 
 #include "../../include/cf_engine.h"
-#include "cf_kernels.h"
 #include "cf_device.h"
+#include "cf_host.h"
+#include "cf_kernels.h"
 #include <thread>
 
 using namespace cfk;
+using namespace cfi;
 
 namespace {
+thread_local std::string g_err;   // cf_last_error
+}  // namespace
 
-thread_local std::string g_err;
+std::atomic<int64_t> cfi::g_live_bytes[2];
 
-int fail(int code, const std::string& msg) {
+// also the errors of the other host translation units (cf_ingest.cpp, the objects)
+int cfi::set_error(int code, const std::string& msg) {
     g_err = msg;
     return code;
 }
-
-#define CF_HIP(expr)                                                                  \
-    do {                                                                              \
-        hipError_t _e = (expr);                                                       \
-        if (_e != hipSuccess)                                                         \
-            return fail(CF_EHIP, std::string(#expr) + ": " + hipGetErrorString(_e));  \
-    } while (0)
-
-#define CF_TRY(expr)            \
-    do {                        \
-        int _r = (expr);        \
-        if (_r != CF_OK) return _r; \
-    } while (0)
-
-// bytes held by live buffers of every engine in the process (cf_debug_live_bytes)
-std::atomic<int64_t> g_live_bytes[2];   // [0] device, [1] pinned host
-
-// The one owner of a device (Pinned: pinned host) allocation; p and cap are in
-// elements.  It never synchronises: a caller that replaces a buffer a stream
-// may still use synchronises first.  A failed allocation clears HIP's sticky
-// error, so the next launch wrapper's hipGetLastError() does not report it.
-template <class T, bool Pinned = false>
-struct Buf {
-    T* p = nullptr;
-    size_t cap = 0;
-    Buf() = default;
-    Buf(Buf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
-    Buf& operator=(Buf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }
-    ~Buf() { release(); }
-    void release() {
-        if (p) (void)(Pinned ? hipHostFree((void*)p) : hipFree((void*)p));
-        g_live_bytes[Pinned] -= (int64_t)(cap * sizeof(T));
-        p = nullptr;
-        cap = 0;
-    }
-    int reset(size_t n, const char* what) {   // always a fresh buffer of exactly n elements
-        release();
-        if (n == 0) return CF_OK;
-        const hipError_t e = Pinned ? hipHostMalloc((void**)&p, n * sizeof(T), hipHostMallocDefault)
-                                    : hipMalloc((void**)&p, n * sizeof(T));
-        if (e != hipSuccess) {
-            p = nullptr;
-            (void)hipGetLastError();
-            return fail(CF_ENOMEM, std::string(Pinned ? "hipHostMalloc(" : "hipMalloc(") + what + ", " +
-                                       std::to_string(n * sizeof(T)) + " B): " + hipGetErrorString(e));
-        }
-        cap = n;
-        g_live_bytes[Pinned] += (int64_t)(n * sizeof(T));
-        return CF_OK;
-    }
-    int reserve(size_t n, const char* what) { return cap >= n ? CF_OK : reset(n, what); }
-    T* get() const { return p; }
-    operator T*() const { return p; }
-};
-template <class T> using DevBuf = Buf<T, false>;
-template <class T> using PinBuf = Buf<T, true>;
-
-}  // namespace
 
 // deterministic range flags kept per step (cf_engine::fx_bad)
 constexpr int kFxSlots = 1024;
@@ -3283,8 +3230,3 @@ int cf_debug_live_bytes(int64_t* device_bytes, int64_t* pinned_bytes) {
 }
 
 }  // extern "C"
-
-// errors of the other host translation units (cf_ingest.cpp)
-namespace cfi {
-int set_error(int code, const std::string& msg) { return fail(code, msg); }
-}  // namespace cfi

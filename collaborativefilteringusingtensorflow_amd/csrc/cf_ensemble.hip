@@ -31,11 +31,8 @@
 
 #include "../../include/cf_engine.h"
 #include "cf_device.h"
+#include "cf_host.h"
 #include "cf_kernels.h"
-
-namespace cfi {
-int set_error(int code, const std::string& msg);  // cf_engine.cpp
-}
 
 namespace cfk {
 
@@ -431,48 +428,17 @@ struct cf_ensemble {
     float reg = 0.f, lr = 0.1f, acc_init = 0.1f;
     int device = 0;
     hipStream_t stream = nullptr;
-    float *U = nullptr, *V = nullptr, *H = nullptr;
-    float *AU = nullptr, *AV = nullptr, *AH = nullptr;
-    float *GU = nullptr, *GV = nullptr, *GH = nullptr;
-    int64_t* indptr = nullptr;
-    int32_t* indices = nullptr;
-    int Bcap = 0;
-    int32_t* uij = nullptr;
-    float* scratch = nullptr;   // si sj wi wj gsi gsj gwi gwj: 8 x [K, B]
-    double* loss_partial = nullptr;
-    double* loss_acc = nullptr;
-    int loss_cap = 0;
+    cfi::DevBuf<float> U, V, H, AU, AV, AH, GU, GV, GH;
+    cfi::DevBuf<int64_t> indptr;
+    cfi::DevBuf<int32_t> indices;
+    cfi::DevBuf<int32_t> uij;       // cf_ens_step: [B, 3]; cf_ens_step_w: pairs [B, 2] | negs [B, W]
+    cfi::DevBuf<float> scratch;     // si sj wi wj gsi gsj gwi gwj: 8 x [K, B]
+    cfi::DevBuf<double> loss_partial;
+    cfi::DevBuf<double> loss_acc;
     std::vector<double> h_loss;
 };
 
 namespace {
-
-template <class T>
-int ealloc(T** p, size_t n) {
-    *p = nullptr;
-    if (n == 0) return CF_OK;
-    if (hipMalloc((void**)p, n * sizeof(T)) != hipSuccess)
-        return cfi::set_error(CF_ENOMEM, "hipMalloc(" + std::to_string(n * sizeof(T)) + " B) failed");
-    return CF_OK;
-}
-
-template <class T>
-void efree(T*& p) {
-    if (p) (void)hipFree((void*)p);
-    p = nullptr;
-}
-
-#define ENS_HIP(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t _e = (expr);                                                                \
-        if (_e != hipSuccess) return cfi::set_error(CF_EHIP, std::string(#expr) + ": " +        \
-                                                                 hipGetErrorString(_e));       \
-    } while (0)
-#define ENS_TRY(expr)           \
-    do {                        \
-        int _r = (expr);        \
-        if (_r != CF_OK) return _r; \
-    } while (0)
 
 float* ens_table(cf_ensemble* e, int t, int64_t* n) {
     const int64_t nu = (int64_t)e->K * e->n_users * e->d, ni = (int64_t)e->K * e->n_items * e->d;
@@ -496,7 +462,7 @@ int dense_apply(cf_ensemble* e, float* X, float* A, float* G, int64_t rows) {
     d.zero_g = 1;
     d.n_rows = rows;
     d.X = X; d.A = A; d.G = G;
-    ENS_HIP(launch_apply_dense(d, e->stream));
+    CF_HIP(launch_apply_dense(d, e->stream));
     return CF_OK;
 }
 
@@ -510,11 +476,7 @@ int cf_ens_create(int64_t n_users, int64_t n_items, int32_t K, int32_t d, float 
         !(lr > 0.f) || !(acc_init > 0.f))
         return cfi::set_error(CF_EINVAL, "bad ensemble configuration (K 1..8, d 1..256)");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return cfi::set_error(CF_EHIP, "no HIP device visible (the engine has no CPU fallback)");
-    if (device < 0 || device >= ndev) return cfi::set_error(CF_EINVAL, "device ordinal out of range");
-    ENS_HIP(hipSetDevice(device));
+    CF_TRY(cfi::open_device(device));
     cf_ensemble* e = new cf_ensemble();
     e->n_users = n_users; e->n_items = n_items; e->K = K; e->d = d;
     e->reg = reg; e->lr = lr; e->acc_init = acc_init; e->device = device;
@@ -523,10 +485,10 @@ int cf_ens_create(int64_t n_users, int64_t n_items, int32_t K, int32_t d, float 
         return bail(cfi::set_error(CF_EHIP, "hipStreamCreate failed"));
     const size_t nu = (size_t)K * n_users * d, ni = (size_t)K * n_items * d, nh = (size_t)K * d;
     int r;
-    if ((r = ealloc(&e->U, nu)) || (r = ealloc(&e->AU, nu)) || (r = ealloc(&e->GU, nu)) ||
-        (r = ealloc(&e->V, ni)) || (r = ealloc(&e->AV, ni)) || (r = ealloc(&e->GV, ni)) ||
-        (r = ealloc(&e->H, nh)) || (r = ealloc(&e->AH, nh)) || (r = ealloc(&e->GH, nh)) ||
-        (r = ealloc(&e->loss_acc, 1)))
+    if ((r = e->U.reset(nu, "U")) || (r = e->AU.reset(nu, "AU")) || (r = e->GU.reset(nu, "GU")) ||
+        (r = e->V.reset(ni, "V")) || (r = e->AV.reset(ni, "AV")) || (r = e->GV.reset(ni, "GV")) ||
+        (r = e->H.reset(nh, "H")) || (r = e->AH.reset(nh, "AH")) || (r = e->GH.reset(nh, "GH")) ||
+        (r = e->loss_acc.reset(1, "loss_acc")))
         return bail(r);
     if (hipMemsetAsync(e->GU, 0, nu * 4, e->stream) != hipSuccess ||
         hipMemsetAsync(e->loss_acc, 0, 8, e->stream) != hipSuccess ||
@@ -542,26 +504,18 @@ int cf_ens_create(int64_t n_users, int64_t n_items, int32_t K, int32_t d, float 
 }
 
 int cf_ens_destroy(cf_ensemble* e) {
-    if (!e) return CF_OK;
-    (void)hipSetDevice(e->device);
-    if (e->stream) (void)hipStreamSynchronize(e->stream);
-    efree(e->U); efree(e->V); efree(e->H); efree(e->AU); efree(e->AV); efree(e->AH);
-    efree(e->GU); efree(e->GV); efree(e->GH); efree(e->indptr); efree(e->indices);
-    efree(e->uij); efree(e->scratch); efree(e->loss_partial); efree(e->loss_acc);
-    if (e->stream) (void)hipStreamDestroy(e->stream);
-    delete e;
-    return CF_OK;
+    return cfi::destroy_object(e);
 }
 
 int cf_ens_init_params(cf_ensemble* e, float mean, float stddev, int32_t truncated, uint64_t seed) {
     if (!e) return cfi::set_error(CF_EINVAL, "null ensemble");
-    ENS_HIP(hipSetDevice(e->device));
+    CF_HIP(hipSetDevice(e->device));
     const int64_t nu = (int64_t)e->K * e->n_users * e->d, ni = (int64_t)e->K * e->n_items * e->d;
-    ENS_HIP(launch_init_normal(e->U, nu, mean, stddev, truncated, mix64(seed ^ 0x11u), e->stream));
-    ENS_HIP(launch_init_normal(e->V, ni, mean, stddev, truncated, mix64(seed ^ 0x22u), e->stream));
-    ENS_HIP(launch_init_normal(e->H, (int64_t)e->K * e->d, mean, stddev, truncated, mix64(seed ^ 0x33u),
+    CF_HIP(launch_init_normal(e->U, nu, mean, stddev, truncated, mix64(seed ^ 0x11u), e->stream));
+    CF_HIP(launch_init_normal(e->V, ni, mean, stddev, truncated, mix64(seed ^ 0x22u), e->stream));
+    CF_HIP(launch_init_normal(e->H, (int64_t)e->K * e->d, mean, stddev, truncated, mix64(seed ^ 0x33u),
                                e->stream));
-    ENS_HIP(hipStreamSynchronize(e->stream));
+    CF_HIP(hipStreamSynchronize(e->stream));
     return CF_OK;
 }
 
@@ -572,43 +526,26 @@ int cf_ens_set_lr(cf_ensemble* e, float lr) {
 }
 
 int cf_ens_set_table(cf_ensemble* e, int32_t t, const float* src, int64_t n) {
-    if (!e || !src) return cfi::set_error(CF_EINVAL, "null argument");
+    if (!e) return cfi::set_error(CF_EINVAL, "null argument");
     int64_t want = 0;
     float* p = ens_table(e, t, &want);
-    if (!p || n != want) return cfi::set_error(CF_EINVAL, "ensemble table size mismatch: want " + std::to_string(want));
-    ENS_HIP(hipSetDevice(e->device));
-    ENS_HIP(hipStreamSynchronize(e->stream));
-    ENS_HIP(hipMemcpy(p, src, (size_t)n * 4, hipMemcpyHostToDevice));
-    return CF_OK;
+    CF_HIP(hipSetDevice(e->device));
+    return cfi::copy_table_in(e->stream, p, want, src, n, "ensemble");
 }
 
 int cf_ens_get_table(cf_ensemble* e, int32_t t, float* dst, int64_t n) {
-    if (!e || !dst) return cfi::set_error(CF_EINVAL, "null argument");
+    if (!e) return cfi::set_error(CF_EINVAL, "null argument");
     int64_t want = 0;
-    float* p = ens_table(e, t, &want);
-    if (!p || n != want) return cfi::set_error(CF_EINVAL, "ensemble table size mismatch: want " + std::to_string(want));
-    ENS_HIP(hipSetDevice(e->device));
-    ENS_HIP(hipStreamSynchronize(e->stream));
-    ENS_HIP(hipMemcpy(dst, p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return CF_OK;
+    const float* p = ens_table(e, t, &want);
+    CF_HIP(hipSetDevice(e->device));
+    return cfi::copy_table_out(e->stream, p, want, dst, n, "ensemble");
 }
 
 int cf_ens_set_interactions(cf_ensemble* e, const int64_t* indptr, const int32_t* indices, int64_t nnz) {
-    if (!e || !indptr || (nnz > 0 && !indices)) return cfi::set_error(CF_EINVAL, "null CSR");
-    if (indptr[0] != 0 || indptr[e->n_users] != nnz) return cfi::set_error(CF_EINVAL, "indptr does not span nnz");
-    for (int64_t u = 0; u < e->n_users; ++u)
-        for (int64_t k = indptr[u]; k < indptr[u + 1]; ++k)
-            if (indices[k] < 0 || indices[k] >= e->n_items || (k > indptr[u] && indices[k - 1] >= indices[k]))
-                return cfi::set_error(CF_EINVAL, "CSR rows must hold sorted, unique, in-range items");
-    ENS_HIP(hipSetDevice(e->device));
-    ENS_HIP(hipStreamSynchronize(e->stream));
-    efree(e->indptr);
-    efree(e->indices);
-    ENS_TRY(ealloc(&e->indptr, (size_t)e->n_users + 1));
-    ENS_TRY(ealloc(&e->indices, (size_t)(nnz > 0 ? nnz : 1)));
-    ENS_HIP(hipMemcpy(e->indptr, indptr, ((size_t)e->n_users + 1) * 8, hipMemcpyHostToDevice));
-    if (nnz > 0) ENS_HIP(hipMemcpy(e->indices, indices, (size_t)nnz * 4, hipMemcpyHostToDevice));
-    return CF_OK;
+    if (!e) return cfi::set_error(CF_EINVAL, "null CSR");
+    CF_TRY(cfi::check_csr(indptr, indices, nnz, e->n_users, e->n_items));
+    CF_HIP(hipSetDevice(e->device));
+    return cfi::upload_csr(e->stream, e->indptr, e->indices, indptr, indices, nnz, e->n_users);
 }
 
 int cf_ens_step(cf_ensemble* e, const int32_t* uij, int32_t B, double* loss_out) {
@@ -619,27 +556,15 @@ int cf_ens_step(cf_ensemble* e, const int32_t* uij, int32_t B, double* loss_out)
         if (uij[3 * p] < 0 || uij[3 * p] >= e->n_users || uij[3 * p + 1] < 0 ||
             uij[3 * p + 1] >= e->n_items || uij[3 * p + 2] < 0 || uij[3 * p + 2] >= e->n_items)
             return cfi::set_error(CF_EINVAL, "triplet " + std::to_string(p) + " out of range");
-    ENS_HIP(hipSetDevice(e->device));
+    CF_HIP(hipSetDevice(e->device));
     const int K = e->K;
     const int npb = (B + kGroupsPerBlock - 1) / kGroupsPerBlock;
     const int nt = (B + kEnsTile - 1) / kEnsTile;
-    if (B > e->Bcap) {
-        ENS_HIP(hipStreamSynchronize(e->stream));
-        efree(e->uij);
-        efree(e->scratch);
-        ENS_TRY(ealloc(&e->uij, (size_t)B * 3));
-        ENS_TRY(ealloc(&e->scratch, (size_t)8 * K * B));
-        e->Bcap = B;
-    }
     const int nl = npb + nt * nt;
-    if (nl > e->loss_cap) {
-        ENS_HIP(hipStreamSynchronize(e->stream));
-        efree(e->loss_partial);
-        ENS_TRY(ealloc(&e->loss_partial, (size_t)nl));
-        e->loss_cap = nl;
-        e->h_loss.resize((size_t)nl);
-    }
-    ENS_HIP(hipMemcpyAsync(e->uij, uij, (size_t)B * 12, hipMemcpyHostToDevice, e->stream));
+    CF_TRY(cfi::grow(e->stream, e->uij, (size_t)B * 3, "uij"));
+    CF_TRY(cfi::grow(e->stream, e->scratch, (size_t)8 * K * B, "scratch"));
+    CF_TRY(cfi::grow(e->stream, e->loss_partial, (size_t)nl, "loss_partial"));
+    CF_HIP(hipMemcpyAsync(e->uij, uij, (size_t)B * 12, hipMemcpyHostToDevice, e->stream));
     EnsArgs a{};
     a.K = K; a.d = e->d; a.B = B;
     a.n_users = e->n_users; a.n_items = e->n_items; a.reg = e->reg;
@@ -651,22 +576,15 @@ int cf_ens_step(cf_ensemble* e, const int32_t* uij, int32_t B, double* loss_out)
     a.loss_partial = e->loss_partial;
     a.loss_acc = e->loss_acc;
     a.n_pair_blocks = npb;
-    ENS_HIP(hipMemsetAsync(a.gsi, 0, 4 * kb * 4, e->stream));
+    CF_HIP(hipMemsetAsync(a.gsi, 0, 4 * kb * 4, e->stream));
     hipLaunchKernelGGL(ens_pair_kernel, dim3(npb), dim3(kBlock), 0, e->stream, a);
     hipLaunchKernelGGL(ens_cross_kernel, dim3(nt, nt), dim3(kBlock), 0, e->stream, a);
     hipLaunchKernelGGL(ens_grad_kernel, dim3(npb), dim3(kBlock), (size_t)K * e->d * 4, e->stream, a);
-    ENS_HIP(hipGetLastError());
-    ENS_TRY(dense_apply(e, e->U, e->AU, e->GU, (int64_t)K * e->n_users));
-    ENS_TRY(dense_apply(e, e->V, e->AV, e->GV, (int64_t)K * e->n_items));
-    ENS_TRY(dense_apply(e, e->H, e->AH, e->GH, K));
-    if (loss_out) {
-        ENS_HIP(hipMemcpyAsync(e->h_loss.data(), e->loss_partial, (size_t)nl * 8, hipMemcpyDeviceToHost,
-                               e->stream));
-        ENS_HIP(hipStreamSynchronize(e->stream));
-        double t = 0.0;
-        for (int q = 0; q < nl; ++q) t += e->h_loss[(size_t)q];
-        *loss_out = t;
-    }
+    CF_HIP(hipGetLastError());
+    CF_TRY(dense_apply(e, e->U, e->AU, e->GU, (int64_t)K * e->n_users));
+    CF_TRY(dense_apply(e, e->V, e->AV, e->GV, (int64_t)K * e->n_items));
+    CF_TRY(dense_apply(e, e->H, e->AH, e->GH, K));
+    if (loss_out) CF_TRY(cfi::read_loss(e->stream, e->loss_partial, nl, e->h_loss, loss_out));
     return CF_OK;
 }
 
@@ -680,27 +598,14 @@ int cf_ens_step_w(cf_ensemble* e, const int32_t* pairs, const int32_t* negs, int
         for (int w = 0; w < W; ++w) ok = ok && negs[(size_t)p * W + w] >= 0 && negs[(size_t)p * W + w] < e->n_items;
         if (!ok) return cfi::set_error(CF_EINVAL, "pair " + std::to_string(p) + " out of range");
     }
-    ENS_HIP(hipSetDevice(e->device));
+    CF_HIP(hipSetDevice(e->device));
     const int K = e->K;
     const int nb = (B + kGroupsPerBlock - 1) / kGroupsPerBlock;
-    const size_t need = (size_t)B * (2 + W);
-    if (need > (size_t)e->Bcap * 3) {   // reuse the uij buffer for [pairs | negs]
-        ENS_HIP(hipStreamSynchronize(e->stream));
-        efree(e->uij);
-        efree(e->scratch);
-        ENS_TRY(ealloc(&e->uij, need));
-        ENS_TRY(ealloc(&e->scratch, (size_t)8 * K * ((need + 2) / 3)));
-        e->Bcap = (int)((need + 2) / 3);
-    }
-    if (nb > e->loss_cap) {
-        ENS_HIP(hipStreamSynchronize(e->stream));
-        efree(e->loss_partial);
-        ENS_TRY(ealloc(&e->loss_partial, (size_t)nb));
-        e->loss_cap = nb;
-        e->h_loss.resize((size_t)nb);
-    }
-    ENS_HIP(hipMemcpyAsync(e->uij, pairs, (size_t)B * 8, hipMemcpyHostToDevice, e->stream));
-    ENS_HIP(hipMemcpyAsync(e->uij + 2 * (size_t)B, negs, (size_t)B * W * 4, hipMemcpyHostToDevice, e->stream));
+    // the uij buffer holds [pairs | negs]; this step takes no scratch
+    CF_TRY(cfi::grow(e->stream, e->uij, (size_t)B * (2 + W), "uij"));
+    CF_TRY(cfi::grow(e->stream, e->loss_partial, (size_t)nb, "loss_partial"));
+    CF_HIP(hipMemcpyAsync(e->uij, pairs, (size_t)B * 8, hipMemcpyHostToDevice, e->stream));
+    CF_HIP(hipMemcpyAsync(e->uij + 2 * (size_t)B, negs, (size_t)B * W * 4, hipMemcpyHostToDevice, e->stream));
     EnsWArgs a{};
     a.K = K; a.d = e->d; a.B = B; a.W = W; a.singles = singles ? 1 : 0;
     a.n_users = e->n_users; a.n_items = e->n_items;
@@ -711,73 +616,33 @@ int cf_ens_step_w(cf_ensemble* e, const int32_t* pairs, const int32_t* negs, int
     a.loss_partial = e->loss_partial;
     a.loss_acc = e->loss_acc;
     hipLaunchKernelGGL(ens_w_kernel, dim3(nb), dim3(kBlock), (size_t)K * e->d * 4, e->stream, a);
-    ENS_HIP(hipGetLastError());
-    ENS_TRY(dense_apply(e, e->U, e->AU, e->GU, (int64_t)K * e->n_users));
-    ENS_TRY(dense_apply(e, e->V, e->AV, e->GV, (int64_t)K * e->n_items));
-    ENS_TRY(dense_apply(e, e->H, e->AH, e->GH, K));
-    if (loss_out) {
-        ENS_HIP(hipMemcpyAsync(e->h_loss.data(), e->loss_partial, (size_t)nb * 8, hipMemcpyDeviceToHost,
-                               e->stream));
-        ENS_HIP(hipStreamSynchronize(e->stream));
-        double t = 0.0;
-        for (int q = 0; q < nb; ++q) t += e->h_loss[(size_t)q];
-        *loss_out = t;
-    }
+    CF_HIP(hipGetLastError());
+    CF_TRY(dense_apply(e, e->U, e->AU, e->GU, (int64_t)K * e->n_users));
+    CF_TRY(dense_apply(e, e->V, e->AV, e->GV, (int64_t)K * e->n_items));
+    CF_TRY(dense_apply(e, e->H, e->AH, e->GH, K));
+    if (loss_out) CF_TRY(cfi::read_loss(e->stream, e->loss_partial, nb, e->h_loss, loss_out));
     return CF_OK;
 }
 
 int cf_ens_take_loss(cf_ensemble* e, double* sum_out) {
     if (!e || !sum_out) return cfi::set_error(CF_EINVAL, "null argument");
-    ENS_HIP(hipSetDevice(e->device));
-    ENS_HIP(hipMemcpyAsync(sum_out, e->loss_acc, 8, hipMemcpyDeviceToHost, e->stream));
-    ENS_HIP(hipMemsetAsync(e->loss_acc, 0, 8, e->stream));
-    ENS_HIP(hipStreamSynchronize(e->stream));
-    return CF_OK;
+    CF_HIP(hipSetDevice(e->device));
+    return cfi::take_loss(e->stream, e->loss_acc, sum_out);
 }
 
 int cf_ens_score_topk(cf_ensemble* e, const int32_t* users, int32_t n, int32_t k, int32_t exclude_train,
                       int32_t* idx_out, float* val_out) {
-    if (!e || n < 0 || !idx_out || (n > 0 && !users)) return cfi::set_error(CF_EINVAL, "bad arguments");
-    if (k < 1 || k > 4096) return cfi::set_error(CF_EINVAL, "k must be 1..4096");
-    if (exclude_train && !e->indptr) return cfi::set_error(CF_ESTATE, "exclude_train needs cf_ens_set_interactions");
-    if (n == 0) return CF_OK;
-    for (int r = 0; r < n; ++r)
-        if (users[r] < 0 || users[r] >= e->n_users) return cfi::set_error(CF_EINVAL, "user id out of range");
-    ENS_HIP(hipSetDevice(e->device));
-    const size_t row_bytes = (size_t)e->n_items * 4;
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)256 << 20) / row_bytes));
-    uint32_t* keys = nullptr;
-    int32_t *d_users = nullptr, *d_idx = nullptr;
-    float* d_val = nullptr;
-    int r;
-    if ((r = ealloc(&keys, (size_t)chunk * e->n_items)) || (r = ealloc(&d_users, (size_t)n)) ||
-        (r = ealloc(&d_idx, (size_t)n * k)) || (r = ealloc(&d_val, (size_t)n * k))) {
-        efree(keys); efree(d_users); efree(d_idx); efree(d_val);
-        return r;
-    }
-    hipError_t he = hipMemcpyAsync(d_users, users, (size_t)n * 4, hipMemcpyHostToDevice, e->stream);
-    for (int u0 = 0; he == hipSuccess && u0 < n; u0 += chunk) {
-        const int m = std::min(chunk, n - u0);
-        const dim3 grid((unsigned)((e->n_items + kBlock - 1) / kBlock), (unsigned)m);
-        hipLaunchKernelGGL(ens_score_kernel, grid, dim3(kBlock), (size_t)2 * e->K * e->d * 4, e->stream,
-                           e->K, e->d, e->n_users, e->n_items, d_users + u0, e->U, e->V, e->H, keys,
-                           exclude_train, e->indptr, e->indices);
-        he = hipGetLastError();
-        if (he != hipSuccess) break;
-        TopkArgs t{};
-        t.k = k;
-        t.n_items = e->n_items;
-        t.keys = keys;
-        t.idx_out = d_idx + (size_t)u0 * k;
-        t.val_out = d_val + (size_t)u0 * k;
-        he = launch_topk(t, m, e->stream);
-    }
-    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-    if (he == hipSuccess) he = hipMemcpy(idx_out, d_idx, (size_t)n * k * 4, hipMemcpyDeviceToHost);
-    if (he == hipSuccess && val_out) he = hipMemcpy(val_out, d_val, (size_t)n * k * 4, hipMemcpyDeviceToHost);
-    efree(keys); efree(d_users); efree(d_idx); efree(d_val);
-    if (he != hipSuccess) return cfi::set_error(CF_EHIP, std::string("cf_ens_score_topk: ") + hipGetErrorString(he));
-    return CF_OK;
+    if (!e) return cfi::set_error(CF_EINVAL, "bad arguments");
+    CF_HIP(hipSetDevice(e->device));
+    return cfi::score_topk_chunks(
+        e->stream, "cf_ens", e->n_users, e->n_items, e->indptr != nullptr, users, n, k, exclude_train, idx_out,
+        val_out, true, [&](const int32_t* d_users, int m, uint32_t* keys, int32_t*, float*) {
+            const dim3 grid((unsigned)((e->n_items + kBlock - 1) / kBlock), (unsigned)m);
+            hipLaunchKernelGGL(ens_score_kernel, grid, dim3(kBlock), (size_t)2 * e->K * e->d * 4, e->stream,
+                               e->K, e->d, e->n_users, e->n_items, d_users, e->U.get(), e->V.get(), e->H.get(),
+                               keys, exclude_train, e->indptr.get(), e->indices.get());
+            return hipGetLastError();
+        });
 }
 
 }  // extern "C"

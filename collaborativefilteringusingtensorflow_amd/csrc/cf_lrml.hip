@@ -42,11 +42,8 @@
 #include <vector>
 
 #include "../../include/cf_engine.h"
+#include "cf_host.h"
 #include "cf_kernels_impl.h"
-
-namespace cfi {
-int set_error(int code, const std::string& msg);  // cf_engine.cpp
-}
 
 namespace cfk {
 
@@ -383,47 +380,18 @@ struct cf_lrml {
     float margin = 0.2f, clip_norm = 1.f, lr = 0.01f, acc_init = 0.1f;
     int device = 0;
     hipStream_t stream = nullptr;
-    float *U = nullptr, *V = nullptr, *Key = nullptr, *Mem = nullptr;
-    float *AU = nullptr, *AV = nullptr, *GU = nullptr, *GV = nullptr;
-    int32_t *cntU = nullptr, *cntV = nullptr;
-    int64_t* indptr = nullptr;
-    int32_t* indices = nullptr;
-    int Bcap = 0;
-    int32_t* ids = nullptr;    // pos [B,2] | neg [B,2] | rankU [2B] | rankV [2B]
-    double* loss_partial = nullptr;
-    double* loss_acc = nullptr;
+    cfi::DevBuf<float> U, V, Key, Mem, AU, AV, GU, GV;
+    cfi::DevBuf<int32_t> cntU, cntV;
+    cfi::DevBuf<int64_t> indptr;
+    cfi::DevBuf<int32_t> indices;
+    cfi::DevBuf<int32_t> ids;    // pos [B,2] | neg [B,2] | rankU [2B] | rankV [2B]
+    cfi::DevBuf<double> loss_partial;
+    cfi::DevBuf<double> loss_acc;
     std::vector<double> h_loss;
     bool clip_pending = true;  // the full-table clip after the next step
 };
 
 namespace {
-
-template <class T>
-int lalloc(T** p, size_t n) {
-    *p = nullptr;
-    if (n == 0) return CF_OK;
-    if (hipMalloc((void**)p, n * sizeof(T)) != hipSuccess)
-        return cfi::set_error(CF_ENOMEM, "hipMalloc(" + std::to_string(n * sizeof(T)) + " B) failed");
-    return CF_OK;
-}
-
-template <class T>
-void lfree(T*& p) {
-    if (p) (void)hipFree((void*)p);
-    p = nullptr;
-}
-
-#define LRML_HIP(expr)                                                                         \
-    do {                                                                                       \
-        hipError_t _e = (expr);                                                                \
-        if (_e != hipSuccess) return cfi::set_error(CF_EHIP, std::string(#expr) + ": " +        \
-                                                                 hipGetErrorString(_e));       \
-    } while (0)
-#define LRML_TRY(expr)              \
-    do {                            \
-        int _r = (expr);            \
-        if (_r != CF_OK) return _r; \
-    } while (0)
 
 float* lrml_table(cf_lrml* e, int t, int64_t* n) {
     const int64_t nu = e->n_users * e->d, ni = e->n_items * e->d, nk = (int64_t)e->d * e->M;
@@ -480,11 +448,7 @@ int cf_lrml_create(int64_t n_users, int64_t n_items, int32_t d, int32_t M, float
     if (d < 1 || d > kLrmlMaxD) return cfi::set_error(CF_EINVAL, "LRML n_factors must be 1..128");
     if (M < 1 || M > kLrmlMaxM) return cfi::set_error(CF_EINVAL, "LRML n_memory must be 1..64");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return cfi::set_error(CF_EHIP, "no HIP device visible (the engine has no CPU fallback)");
-    if (device < 0 || device >= ndev) return cfi::set_error(CF_EINVAL, "device ordinal out of range");
-    LRML_HIP(hipSetDevice(device));
+    CF_TRY(cfi::open_device(device));
     cf_lrml* e = new cf_lrml();
     e->n_users = n_users; e->n_items = n_items; e->d = d; e->M = M;
     e->margin = margin; e->clip_norm = clip_norm; e->lr = lr; e->acc_init = acc_init; e->device = device;
@@ -493,11 +457,11 @@ int cf_lrml_create(int64_t n_users, int64_t n_items, int32_t d, int32_t M, float
         return bail(cfi::set_error(CF_EHIP, "hipStreamCreate failed"));
     const size_t nu = (size_t)n_users * d, ni = (size_t)n_items * d, nk = (size_t)d * M;
     int r;
-    if ((r = lalloc(&e->U, nu)) || (r = lalloc(&e->AU, nu)) || (r = lalloc(&e->GU, nu)) ||
-        (r = lalloc(&e->V, ni)) || (r = lalloc(&e->AV, ni)) || (r = lalloc(&e->GV, ni)) ||
-        (r = lalloc(&e->Key, nk)) || (r = lalloc(&e->Mem, nk)) ||
-        (r = lalloc(&e->cntU, (size_t)n_users)) || (r = lalloc(&e->cntV, (size_t)n_items)) ||
-        (r = lalloc(&e->loss_acc, 1)))
+    if ((r = e->U.reset(nu, "U")) || (r = e->AU.reset(nu, "AU")) || (r = e->GU.reset(nu, "GU")) ||
+        (r = e->V.reset(ni, "V")) || (r = e->AV.reset(ni, "AV")) || (r = e->GV.reset(ni, "GV")) ||
+        (r = e->Key.reset(nk, "Key")) || (r = e->Mem.reset(nk, "Mem")) ||
+        (r = e->cntU.reset((size_t)n_users, "cntU")) || (r = e->cntV.reset((size_t)n_items, "cntV")) ||
+        (r = e->loss_acc.reset(1, "loss_acc")))
         return bail(r);
     if (hipMemsetAsync(e->U, 0, nu * 4, e->stream) != hipSuccess ||
         hipMemsetAsync(e->V, 0, ni * 4, e->stream) != hipSuccess ||
@@ -517,72 +481,46 @@ int cf_lrml_create(int64_t n_users, int64_t n_items, int32_t d, int32_t M, float
 }
 
 int cf_lrml_destroy(cf_lrml* e) {
-    if (!e) return CF_OK;
-    (void)hipSetDevice(e->device);
-    if (e->stream) (void)hipStreamSynchronize(e->stream);
-    lfree(e->U); lfree(e->V); lfree(e->Key); lfree(e->Mem); lfree(e->AU); lfree(e->AV);
-    lfree(e->GU); lfree(e->GV); lfree(e->cntU); lfree(e->cntV); lfree(e->indptr); lfree(e->indices);
-    lfree(e->ids); lfree(e->loss_partial); lfree(e->loss_acc);
-    if (e->stream) (void)hipStreamDestroy(e->stream);
-    delete e;
-    return CF_OK;
+    return cfi::destroy_object(e);
 }
 
 int cf_lrml_init_params(cf_lrml* e, float mean, float stddev, uint64_t seed) {
     if (!e) return cfi::set_error(CF_EINVAL, "null LRML object");
-    LRML_HIP(hipSetDevice(e->device));
+    CF_HIP(hipSetDevice(e->device));
     const int64_t nk = (int64_t)e->d * e->M;
     // tf.random_normal_initializer on all four tables (lrml.py:30-41): not truncated
-    LRML_HIP(launch_init_normal(e->U, e->n_users * e->d, mean, stddev, 0, mix64(seed ^ 0x11u), e->stream));
-    LRML_HIP(launch_init_normal(e->V, e->n_items * e->d, mean, stddev, 0, mix64(seed ^ 0x22u), e->stream));
-    LRML_HIP(launch_init_normal(e->Key, nk, mean, stddev, 0, mix64(seed ^ 0x33u), e->stream));
-    LRML_HIP(launch_init_normal(e->Mem, nk, mean, stddev, 0, mix64(seed ^ 0x44u), e->stream));
-    LRML_HIP(hipStreamSynchronize(e->stream));
+    CF_HIP(launch_init_normal(e->U, e->n_users * e->d, mean, stddev, 0, mix64(seed ^ 0x11u), e->stream));
+    CF_HIP(launch_init_normal(e->V, e->n_items * e->d, mean, stddev, 0, mix64(seed ^ 0x22u), e->stream));
+    CF_HIP(launch_init_normal(e->Key, nk, mean, stddev, 0, mix64(seed ^ 0x33u), e->stream));
+    CF_HIP(launch_init_normal(e->Mem, nk, mean, stddev, 0, mix64(seed ^ 0x44u), e->stream));
+    CF_HIP(hipStreamSynchronize(e->stream));
     e->clip_pending = true;
     return CF_OK;
 }
 
 int cf_lrml_set_table(cf_lrml* e, int32_t t, const float* src, int64_t n) {
-    if (!e || !src) return cfi::set_error(CF_EINVAL, "null argument");
+    if (!e) return cfi::set_error(CF_EINVAL, "null argument");
     int64_t want = 0;
     float* p = lrml_table(e, t, &want);
-    if (!p || n != want) return cfi::set_error(CF_EINVAL, "LRML table size mismatch: want " + std::to_string(want));
-    LRML_HIP(hipSetDevice(e->device));
-    LRML_HIP(hipStreamSynchronize(e->stream));
-    LRML_HIP(hipMemcpy(p, src, (size_t)n * 4, hipMemcpyHostToDevice));
+    CF_HIP(hipSetDevice(e->device));
+    CF_TRY(cfi::copy_table_in(e->stream, p, want, src, n, "LRML"));
     if (t <= 1) e->clip_pending = true;
     return CF_OK;
 }
 
 int cf_lrml_get_table(cf_lrml* e, int32_t t, float* dst, int64_t n) {
-    if (!e || !dst) return cfi::set_error(CF_EINVAL, "null argument");
+    if (!e) return cfi::set_error(CF_EINVAL, "null argument");
     int64_t want = 0;
-    float* p = lrml_table(e, t, &want);
-    if (!p || n != want) return cfi::set_error(CF_EINVAL, "LRML table size mismatch: want " + std::to_string(want));
-    LRML_HIP(hipSetDevice(e->device));
-    LRML_HIP(hipStreamSynchronize(e->stream));
-    LRML_HIP(hipMemcpy(dst, p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return CF_OK;
+    const float* p = lrml_table(e, t, &want);
+    CF_HIP(hipSetDevice(e->device));
+    return cfi::copy_table_out(e->stream, p, want, dst, n, "LRML");
 }
 
 int cf_lrml_set_interactions(cf_lrml* e, const int64_t* indptr, const int32_t* indices, int64_t nnz) {
-    if (!e || !indptr || (nnz > 0 && !indices)) return cfi::set_error(CF_EINVAL, "null CSR");
-    if (indptr[0] != 0 || indptr[e->n_users] != nnz) return cfi::set_error(CF_EINVAL, "indptr does not span nnz");
-    for (int64_t u = 0; u < e->n_users; ++u) {
-        if (indptr[u + 1] < indptr[u]) return cfi::set_error(CF_EINVAL, "indptr not monotone");
-        for (int64_t k = indptr[u]; k < indptr[u + 1]; ++k)
-            if (indices[k] < 0 || indices[k] >= e->n_items || (k > indptr[u] && indices[k - 1] >= indices[k]))
-                return cfi::set_error(CF_EINVAL, "CSR rows must hold sorted, unique, in-range items");
-    }
-    LRML_HIP(hipSetDevice(e->device));
-    LRML_HIP(hipStreamSynchronize(e->stream));
-    lfree(e->indptr);
-    lfree(e->indices);
-    LRML_TRY(lalloc(&e->indptr, (size_t)e->n_users + 1));
-    LRML_TRY(lalloc(&e->indices, (size_t)(nnz > 0 ? nnz : 1)));
-    LRML_HIP(hipMemcpy(e->indptr, indptr, ((size_t)e->n_users + 1) * 8, hipMemcpyHostToDevice));
-    if (nnz > 0) LRML_HIP(hipMemcpy(e->indices, indices, (size_t)nnz * 4, hipMemcpyHostToDevice));
-    return CF_OK;
+    if (!e) return cfi::set_error(CF_EINVAL, "null CSR");
+    CF_TRY(cfi::check_csr(indptr, indices, nnz, e->n_users, e->n_items));
+    CF_HIP(hipSetDevice(e->device));
+    return cfi::upload_csr(e->stream, e->indptr, e->indices, indptr, indices, nnz, e->n_users);
 }
 
 int cf_lrml_step(cf_lrml* e, const int32_t* pos, const int32_t* neg, int32_t B, double* loss_out) {
@@ -594,20 +532,12 @@ int cf_lrml_step(cf_lrml* e, const int32_t* pos, const int32_t* neg, int32_t B, 
         if (neg[2 * p] < 0 || neg[2 * p] >= e->n_users || neg[2 * p + 1] < 0 || neg[2 * p + 1] >= e->n_items)
             return cfi::set_error(CF_EINVAL, "negative pair " + std::to_string(p) + " out of range");
     }
-    LRML_HIP(hipSetDevice(e->device));
+    CF_HIP(hipSetDevice(e->device));
     const int nb = (B + kGroupsPerBlock - 1) / kGroupsPerBlock;
-    if (B > e->Bcap) {
-        LRML_HIP(hipStreamSynchronize(e->stream));
-        lfree(e->ids);
-        lfree(e->loss_partial);
-        e->Bcap = 0;
-        LRML_TRY(lalloc(&e->ids, (size_t)B * 8));
-        LRML_TRY(lalloc(&e->loss_partial, (size_t)nb));
-        e->Bcap = B;
-        e->h_loss.resize((size_t)nb);
-    }
-    LRML_HIP(hipMemcpyAsync(e->ids, pos, (size_t)B * 8, hipMemcpyHostToDevice, e->stream));
-    LRML_HIP(hipMemcpyAsync(e->ids + 2 * (size_t)B, neg, (size_t)B * 8, hipMemcpyHostToDevice, e->stream));
+    CF_TRY(cfi::grow(e->stream, e->ids, (size_t)B * 8, "ids"));
+    CF_TRY(cfi::grow(e->stream, e->loss_partial, (size_t)nb, "loss_partial"));
+    CF_HIP(hipMemcpyAsync(e->ids, pos, (size_t)B * 8, hipMemcpyHostToDevice, e->stream));
+    CF_HIP(hipMemcpyAsync(e->ids + 2 * (size_t)B, neg, (size_t)B * 8, hipMemcpyHostToDevice, e->stream));
     LrmlArgs a{};
     a.d = e->d; a.M = e->M; a.B = B;
     a.margin = e->margin; a.lr = e->lr; a.clip_norm = e->clip_norm;
@@ -619,83 +549,43 @@ int cf_lrml_step(cf_lrml* e, const int32_t* pos, const int32_t* neg, int32_t B, 
     a.cntU = e->cntU; a.cntV = e->cntV;
     a.loss_partial = e->loss_partial;
     a.loss_acc = e->loss_acc;
-    LRML_HIP(launch_lrml_step(e, a, nb));
-    LRML_HIP(launch_lrml_apply(e, a));
+    CF_HIP(launch_lrml_step(e, a, nb));
+    CF_HIP(launch_lrml_apply(e, a));
     if (e->clip_pending) {   // lrml.py:106-109 clips every row; later steps: fixed points
-        LRML_HIP(launch_clip_full(e->U, e->n_users, e->d, e->clip_norm, e->stream));
-        LRML_HIP(launch_clip_full(e->V, e->n_items, e->d, e->clip_norm, e->stream));
+        CF_HIP(launch_clip_full(e->U, e->n_users, e->d, e->clip_norm, e->stream));
+        CF_HIP(launch_clip_full(e->V, e->n_items, e->d, e->clip_norm, e->stream));
         e->clip_pending = false;
     }
-    if (loss_out) {
-        LRML_HIP(hipMemcpyAsync(e->h_loss.data(), e->loss_partial, (size_t)nb * 8, hipMemcpyDeviceToHost,
-                                e->stream));
-        LRML_HIP(hipStreamSynchronize(e->stream));
-        double t = 0.0;
-        for (int q = 0; q < nb; ++q) t += e->h_loss[(size_t)q];
-        *loss_out = t;
-    }
+    if (loss_out) CF_TRY(cfi::read_loss(e->stream, e->loss_partial, nb, e->h_loss, loss_out));
     return CF_OK;
 }
 
 int cf_lrml_take_loss(cf_lrml* e, double* sum_out) {
     if (!e || !sum_out) return cfi::set_error(CF_EINVAL, "null argument");
-    LRML_HIP(hipSetDevice(e->device));
-    LRML_HIP(hipMemcpyAsync(sum_out, e->loss_acc, 8, hipMemcpyDeviceToHost, e->stream));
-    LRML_HIP(hipMemsetAsync(e->loss_acc, 0, 8, e->stream));
-    LRML_HIP(hipStreamSynchronize(e->stream));
-    return CF_OK;
+    CF_HIP(hipSetDevice(e->device));
+    return cfi::take_loss(e->stream, e->loss_acc, sum_out);
 }
 
 int cf_lrml_score_topk(cf_lrml* e, const int32_t* users, int32_t n, int32_t k, int32_t exclude_train,
                        int32_t predict_mode, int32_t* idx_out, float* val_out) {
-    if (!e || n < 0 || !idx_out || (n > 0 && !users)) return cfi::set_error(CF_EINVAL, "bad arguments");
-    if (k < 1 || k > 4096) return cfi::set_error(CF_EINVAL, "k must be 1..4096");
+    if (!e) return cfi::set_error(CF_EINVAL, "bad arguments");
     if (predict_mode != CF_LRML_REFERENCE && predict_mode != CF_LRML_TRAIN)
         return cfi::set_error(CF_EINVAL, "predict_mode must be CF_LRML_REFERENCE or CF_LRML_TRAIN");
-    if (exclude_train && !e->indptr) return cfi::set_error(CF_ESTATE, "exclude_train needs cf_lrml_set_interactions");
-    if (n == 0) return CF_OK;
-    for (int r = 0; r < n; ++r)
-        if (users[r] < 0 || users[r] >= e->n_users) return cfi::set_error(CF_EINVAL, "user id out of range");
-    LRML_HIP(hipSetDevice(e->device));
-    const size_t row_bytes = (size_t)e->n_items * 4;
-    const int chunk = (int)std::max<size_t>(
-        1, std::min<size_t>(std::min<size_t>((size_t)n, 65535), ((size_t)256 << 20) / row_bytes));
-    uint32_t* keys = nullptr;
-    int32_t *d_users = nullptr, *d_idx = nullptr;
-    float* d_val = nullptr;
-    int r;
-    if ((r = lalloc(&keys, (size_t)chunk * e->n_items)) || (r = lalloc(&d_users, (size_t)n)) ||
-        (r = lalloc(&d_idx, (size_t)n * k)) || (r = lalloc(&d_val, (size_t)n * k))) {
-        lfree(keys); lfree(d_users); lfree(d_idx); lfree(d_val);
-        return r;
-    }
-    hipError_t he = hipMemcpyAsync(d_users, users, (size_t)n * 4, hipMemcpyHostToDevice, e->stream);
-    for (int u0 = 0; he == hipSuccess && u0 < n; u0 += chunk) {
-        const int m = std::min(chunk, n - u0);
-        const dim3 grid((unsigned)((e->n_items + kLrmlScoreItems - 1) / kLrmlScoreItems), (unsigned)m);
-        LrmlScoreArgs a{};
-        a.d = e->d; a.M = e->M; a.n_items = e->n_items;
-        a.users = d_users + u0;
-        a.U = e->U; a.V = e->V; a.Key = e->Key; a.Mem = e->Mem;
-        a.keys = keys;
-        a.exclude_train = exclude_train;
-        a.indptr = e->indptr; a.indices = e->indices;
-        he = predict_mode == CF_LRML_TRAIN ? launch_lrml_score_m<1>(e, a, grid) : launch_lrml_score_m<0>(e, a, grid);
-        if (he != hipSuccess) break;
-        TopkArgs t{};
-        t.k = k;
-        t.n_items = e->n_items;
-        t.keys = keys;
-        t.idx_out = d_idx + (size_t)u0 * k;
-        t.val_out = d_val + (size_t)u0 * k;
-        he = launch_topk(t, m, e->stream);
-    }
-    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-    if (he == hipSuccess) he = hipMemcpy(idx_out, d_idx, (size_t)n * k * 4, hipMemcpyDeviceToHost);
-    if (he == hipSuccess && val_out) he = hipMemcpy(val_out, d_val, (size_t)n * k * 4, hipMemcpyDeviceToHost);
-    lfree(keys); lfree(d_users); lfree(d_idx); lfree(d_val);
-    if (he != hipSuccess) return cfi::set_error(CF_EHIP, std::string("cf_lrml_score_topk: ") + hipGetErrorString(he));
-    return CF_OK;
+    CF_HIP(hipSetDevice(e->device));
+    return cfi::score_topk_chunks(
+        e->stream, "cf_lrml", e->n_users, e->n_items, e->indptr != nullptr, users, n, k, exclude_train, idx_out,
+        val_out, true, [&](const int32_t* d_users, int m, uint32_t* keys, int32_t*, float*) {
+            const dim3 grid((unsigned)((e->n_items + kLrmlScoreItems - 1) / kLrmlScoreItems), (unsigned)m);
+            LrmlScoreArgs a{};
+            a.d = e->d; a.M = e->M; a.n_items = e->n_items;
+            a.users = d_users;
+            a.U = e->U; a.V = e->V; a.Key = e->Key; a.Mem = e->Mem;
+            a.keys = keys;
+            a.exclude_train = exclude_train;
+            a.indptr = e->indptr; a.indices = e->indices;
+            return predict_mode == CF_LRML_TRAIN ? launch_lrml_score_m<1>(e, a, grid)
+                                                 : launch_lrml_score_m<0>(e, a, grid);
+        });
 }
 
 }  // extern "C"

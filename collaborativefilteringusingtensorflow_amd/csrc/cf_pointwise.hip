@@ -49,11 +49,8 @@
 #include <vector>
 
 #include "../../include/cf_engine.h"
+#include "cf_host.h"
 #include "cf_kernels_impl.h"
-
-namespace cfi {
-int set_error(int code, const std::string& msg);  // cf_engine.cpp
-}
 
 namespace cfk {
 
@@ -441,47 +438,43 @@ struct cf_pw {
     float weight = 1.f, s = 1.f, reg = 0.f, lr = 0.1f, acc_init = 0.1f;
     int device = 0;
     hipStream_t stream = nullptr;
-    float *U = nullptr, *V = nullptr, *K = nullptr, *AU = nullptr, *AV = nullptr, *AK = nullptr;
-    int64_t* indptr = nullptr;
-    int32_t* indices = nullptr;
-    int Bcap = 0;
-    int32_t* meta = nullptr;     // the step's host-built arrays (see cf_pw_step)
-    float* part = nullptr;       // [2 Bcap, d]
-    double* kpart = nullptr;     // [min(kPwMaxBlocks, tiles of Bcap), Dp * Dp], SVD
-    double* loss_partial = nullptr;
-    double* loss_acc = nullptr;
+    cfi::DevBuf<float> U, V, K, AU, AV, AK;
+    cfi::DevBuf<int64_t> indptr;
+    cfi::DevBuf<int32_t> indices;
+    cfi::DevBuf<int32_t> meta;          // the step's host-built arrays (PwMeta)
+    cfi::DevBuf<float> part;            // [2 B, d]
+    cfi::DevBuf<double> kpart;          // [min(kPwMaxBlocks, tiles), Dp * Dp], SVD
+    cfi::DevBuf<double> loss_partial;   // [tiles]
+    cfi::DevBuf<double> loss_acc;
     std::vector<double> h_loss;
     std::vector<int32_t> h_meta, ucnt, icnt, upos;   // ucnt / icnt: zero between steps
 };
 
 namespace {
 
-template <class T>
-int palloc(T** p, size_t n) {
-    *p = nullptr;
-    if (n == 0) return CF_OK;
-    if (hipMalloc((void**)p, n * sizeof(T)) != hipSuccess)
-        return cfi::set_error(CF_ENOMEM, "hipMalloc(" + std::to_string(n * sizeof(T)) + " B) failed");
-    return CF_OK;
+// one allocation of 14 B + 1 words carved into the step's arrays, on the host and on the device
+struct PwMeta {
+    int32_t* ui;        // [B, 2] the batch ordered by user
+    float* r;           // [B]
+    int32_t *ustart, *ulen, *icnt;   // [B] each
+    int32_t *def_row, *def_n;        // [2 B] each
+    int32_t* def_ptr;   // [2 B + 1]
+    int32_t* def_pos;   // [2 B]
+};
+constexpr size_t pw_meta_words(int B) { return (size_t)14 * B + 1; }
+PwMeta pw_meta(int32_t* base, int B) {
+    PwMeta m;
+    m.ui = base;
+    m.r = reinterpret_cast<float*>(base + 2 * (size_t)B);
+    m.ustart = base + 3 * (size_t)B;
+    m.ulen = m.ustart + B;
+    m.icnt = m.ulen + B;
+    m.def_row = m.icnt + B;
+    m.def_n = m.def_row + 2 * (size_t)B;
+    m.def_ptr = m.def_n + 2 * (size_t)B;
+    m.def_pos = m.def_ptr + 2 * (size_t)B + 1;
+    return m;
 }
-
-template <class T>
-void pfree(T*& p) {
-    if (p) (void)hipFree((void*)p);
-    p = nullptr;
-}
-
-#define PW_HIP(expr)                                                                           \
-    do {                                                                                       \
-        hipError_t _e = (expr);                                                                \
-        if (_e != hipSuccess) return cfi::set_error(CF_EHIP, std::string(#expr) + ": " +        \
-                                                                 hipGetErrorString(_e));       \
-    } while (0)
-#define PW_TRY(expr)                \
-    do {                            \
-        int _r = (expr);            \
-        if (_r != CF_OK) return _r; \
-    } while (0)
 
 float* pw_table(cf_pw* e, int t, int64_t* n) {
     const int64_t nu = e->n_users * e->d, ni = e->n_items * e->d;
@@ -543,11 +536,7 @@ int cf_pw_create(int64_t n_users, int64_t n_items, int32_t d, int32_t kind, floa
     if (kind != CF_PW_MF && kind != CF_PW_SVD) return cfi::set_error(CF_EINVAL, "kind must be CF_PW_MF or CF_PW_SVD");
     if (kind == CF_PW_SVD && weight != 1.f) return cfi::set_error(CF_EINVAL, "SVD takes weight 1");
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
-        return cfi::set_error(CF_EHIP, "no HIP device visible (the engine has no CPU fallback)");
-    if (device < 0 || device >= ndev) return cfi::set_error(CF_EINVAL, "device ordinal out of range");
-    PW_HIP(hipSetDevice(device));
+    CF_TRY(cfi::open_device(device));
     cf_pw* e = new cf_pw();
     e->n_users = n_users; e->n_items = n_items; e->d = d; e->Dp = (d + 15) & ~15; e->kind = kind;
     e->weight = weight; e->s = (float)std::sqrt((double)weight);   // np.sqrt(weight) as a float32 constant
@@ -561,9 +550,9 @@ int cf_pw_create(int64_t n_users, int64_t n_items, int32_t d, int32_t kind, floa
     const size_t nu = (size_t)n_users * d, ni = (size_t)n_items * d;
     const size_t nk = kind == CF_PW_SVD ? (size_t)d * d : 0;
     int r;
-    if ((r = palloc(&e->U, nu)) || (r = palloc(&e->AU, nu)) || (r = palloc(&e->V, ni)) ||
-        (r = palloc(&e->AV, ni)) || (r = palloc(&e->K, nk)) || (r = palloc(&e->AK, nk)) ||
-        (r = palloc(&e->loss_acc, 1)))
+    if ((r = e->U.reset(nu, "U")) || (r = e->AU.reset(nu, "AU")) || (r = e->V.reset(ni, "V")) ||
+        (r = e->AV.reset(ni, "AV")) || (r = e->K.reset(nk, "K")) || (r = e->AK.reset(nk, "AK")) ||
+        (r = e->loss_acc.reset(1, "loss_acc")))
         return bail(r);
     if (hipMemsetAsync(e->U, 0, nu * 4, e->stream) != hipSuccess ||
         hipMemsetAsync(e->V, 0, ni * 4, e->stream) != hipSuccess ||
@@ -579,26 +568,18 @@ int cf_pw_create(int64_t n_users, int64_t n_items, int32_t d, int32_t kind, floa
 }
 
 int cf_pw_destroy(cf_pw* e) {
-    if (!e) return CF_OK;
-    (void)hipSetDevice(e->device);
-    if (e->stream) (void)hipStreamSynchronize(e->stream);
-    pfree(e->U); pfree(e->V); pfree(e->K); pfree(e->AU); pfree(e->AV); pfree(e->AK);
-    pfree(e->indptr); pfree(e->indices); pfree(e->meta); pfree(e->part); pfree(e->kpart);
-    pfree(e->loss_partial); pfree(e->loss_acc);
-    if (e->stream) (void)hipStreamDestroy(e->stream);
-    delete e;
-    return CF_OK;
+    return cfi::destroy_object(e);
 }
 
 int cf_pw_init_params(cf_pw* e, float mean, float stddev, int32_t truncated, uint64_t seed) {
     if (!e) return cfi::set_error(CF_EINVAL, "null pointwise object");
-    PW_HIP(hipSetDevice(e->device));
+    CF_HIP(hipSetDevice(e->device));
     const int tr = truncated ? 1 : 0;   // tf.truncated_normal_initializer on every table (mf.py:26-31, svd.py:26-34)
-    PW_HIP(launch_init_normal(e->U, e->n_users * e->d, mean, stddev, tr, mix64(seed ^ 0x51u), e->stream));
-    PW_HIP(launch_init_normal(e->V, e->n_items * e->d, mean, stddev, tr, mix64(seed ^ 0x52u), e->stream));
+    CF_HIP(launch_init_normal(e->U, e->n_users * e->d, mean, stddev, tr, mix64(seed ^ 0x51u), e->stream));
+    CF_HIP(launch_init_normal(e->V, e->n_items * e->d, mean, stddev, tr, mix64(seed ^ 0x52u), e->stream));
     if (e->kind == CF_PW_SVD)
-        PW_HIP(launch_init_normal(e->K, (int64_t)e->d * e->d, mean, stddev, tr, mix64(seed ^ 0x53u), e->stream));
-    PW_HIP(hipStreamSynchronize(e->stream));
+        CF_HIP(launch_init_normal(e->K, (int64_t)e->d * e->d, mean, stddev, tr, mix64(seed ^ 0x53u), e->stream));
+    CF_HIP(hipStreamSynchronize(e->stream));
     return CF_OK;
 }
 
@@ -607,11 +588,8 @@ int cf_pw_set_table(cf_pw* e, int32_t t, const float* src, int64_t n) {
     int64_t want = 0;
     float* p = pw_table(e, t, &want);
     if (!p) return cfi::set_error(CF_EINVAL, "no such pointwise table (K and AK: SVD only)");
-    if (n != want) return cfi::set_error(CF_EINVAL, "pointwise table size mismatch: want " + std::to_string(want));
-    PW_HIP(hipSetDevice(e->device));
-    PW_HIP(hipStreamSynchronize(e->stream));
-    PW_HIP(hipMemcpy(p, src, (size_t)n * 4, hipMemcpyHostToDevice));
-    return CF_OK;
+    CF_HIP(hipSetDevice(e->device));
+    return cfi::copy_table_in(e->stream, p, want, src, n, "pointwise");
 }
 
 int cf_pw_get_table(cf_pw* e, int32_t t, float* dst, int64_t n) {
@@ -619,31 +597,15 @@ int cf_pw_get_table(cf_pw* e, int32_t t, float* dst, int64_t n) {
     int64_t want = 0;
     float* p = pw_table(e, t, &want);
     if (!p) return cfi::set_error(CF_EINVAL, "no such pointwise table (K and AK: SVD only)");
-    if (n != want) return cfi::set_error(CF_EINVAL, "pointwise table size mismatch: want " + std::to_string(want));
-    PW_HIP(hipSetDevice(e->device));
-    PW_HIP(hipStreamSynchronize(e->stream));
-    PW_HIP(hipMemcpy(dst, p, (size_t)n * 4, hipMemcpyDeviceToHost));
-    return CF_OK;
+    CF_HIP(hipSetDevice(e->device));
+    return cfi::copy_table_out(e->stream, p, want, dst, n, "pointwise");
 }
 
 int cf_pw_set_interactions(cf_pw* e, const int64_t* indptr, const int32_t* indices, int64_t nnz) {
-    if (!e || !indptr || (nnz > 0 && !indices)) return cfi::set_error(CF_EINVAL, "null CSR");
-    if (indptr[0] != 0 || indptr[e->n_users] != nnz) return cfi::set_error(CF_EINVAL, "indptr does not span nnz");
-    for (int64_t u = 0; u < e->n_users; ++u) {
-        if (indptr[u + 1] < indptr[u]) return cfi::set_error(CF_EINVAL, "indptr not monotone");
-        for (int64_t k = indptr[u]; k < indptr[u + 1]; ++k)
-            if (indices[k] < 0 || indices[k] >= e->n_items || (k > indptr[u] && indices[k - 1] >= indices[k]))
-                return cfi::set_error(CF_EINVAL, "CSR rows must hold sorted, unique, in-range items");
-    }
-    PW_HIP(hipSetDevice(e->device));
-    PW_HIP(hipStreamSynchronize(e->stream));
-    pfree(e->indptr);
-    pfree(e->indices);
-    PW_TRY(palloc(&e->indptr, (size_t)e->n_users + 1));
-    PW_TRY(palloc(&e->indices, (size_t)(nnz > 0 ? nnz : 1)));
-    PW_HIP(hipMemcpy(e->indptr, indptr, ((size_t)e->n_users + 1) * 8, hipMemcpyHostToDevice));
-    if (nnz > 0) PW_HIP(hipMemcpy(e->indices, indices, (size_t)nnz * 4, hipMemcpyHostToDevice));
-    return CF_OK;
+    if (!e) return cfi::set_error(CF_EINVAL, "null CSR");
+    CF_TRY(cfi::check_csr(indptr, indices, nnz, e->n_users, e->n_items));
+    CF_HIP(hipSetDevice(e->device));
+    return cfi::upload_csr(e->stream, e->indptr, e->indices, indptr, indices, nnz, e->n_users);
 }
 
 int cf_pw_step(cf_pw* e, const int32_t* ui, const float* r, int32_t B, double* loss_out) {
@@ -654,38 +616,22 @@ int cf_pw_step(cf_pw* e, const int32_t* ui, const float* r, int32_t B, double* l
             return cfi::set_error(CF_EINVAL, "row " + std::to_string(p) + " out of range");
         if (!std::isfinite(r[p])) return cfi::set_error(CF_EINVAL, "rating " + std::to_string(p) + " is not finite");
     }
-    PW_HIP(hipSetDevice(e->device));
+    CF_HIP(hipSetDevice(e->device));
     const int tiles = (B + kPwTile - 1) / kPwTile;
     const bool svd = e->kind == CF_PW_SVD;
     const int tpb = svd ? (tiles + kPwMaxBlocks - 1) / kPwMaxBlocks : 1;
     const int blocks = (tiles + tpb - 1) / tpb;
-    if (B > e->Bcap) {
-        PW_HIP(hipStreamSynchronize(e->stream));
-        pfree(e->meta); pfree(e->part); pfree(e->loss_partial);
-        e->Bcap = 0;
-        // ui 2B | r B | ustart B | ulen B | icnt B | def_row 2B | def_n 2B | def_ptr 2B + 1 | def_pos 2B
-        PW_TRY(palloc(&e->meta, (size_t)14 * B + 1));
-        PW_TRY(palloc(&e->part, (size_t)2 * B * e->d));
-        PW_TRY(palloc(&e->loss_partial, (size_t)tiles));
-        pfree(e->kpart);
-        // the block count is not monotone in B (513 tiles: 257 blocks, 512 tiles: 512): size for
-        // the most any B <= Bcap can launch
-        if (svd) PW_TRY(palloc(&e->kpart, (size_t)std::min(kPwMaxBlocks, tiles) * e->Dp * e->Dp));
-        e->Bcap = B;
-        e->h_loss.resize((size_t)tiles);
-    }
+    CF_TRY(cfi::grow(e->stream, e->meta, pw_meta_words(B), "meta"));
+    CF_TRY(cfi::grow(e->stream, e->part, (size_t)2 * B * e->d, "part"));
+    CF_TRY(cfi::grow(e->stream, e->loss_partial, (size_t)tiles, "loss_partial"));
+    // the block count is not monotone in B (513 tiles: 257 blocks, 512 tiles: 512); this bound is
+    if (svd) CF_TRY(cfi::grow(e->stream, e->kpart, (size_t)std::min(kPwMaxBlocks, tiles) * e->Dp * e->Dp, "kpart"));
     // the batch ordered by user: users in order of first appearance, a user's rows in batch order
-    std::vector<int32_t>& m = e->h_meta;
-    m.assign((size_t)14 * B + 1, 0);
-    int32_t* s_ui = m.data();
-    float* s_r = reinterpret_cast<float*>(m.data() + 2 * (size_t)B);
-    int32_t* ustart = m.data() + 3 * (size_t)B;
-    int32_t* ulen = ustart + B;
-    int32_t* icnt = ulen + B;
-    int32_t* def_row = icnt + B;
-    int32_t* def_n = def_row + 2 * (size_t)B;
-    int32_t* def_ptr = def_n + 2 * (size_t)B;
-    int32_t* def_pos = def_ptr + 2 * (size_t)B + 1;
+    e->h_meta.assign(pw_meta_words(B), 0);
+    const PwMeta m = pw_meta(e->h_meta.data(), B);
+    int32_t *const s_ui = m.ui, *const ustart = m.ustart, *const ulen = m.ulen, *const icnt = m.icnt;
+    int32_t *const def_row = m.def_row, *const def_n = m.def_n, *const def_ptr = m.def_ptr, *const def_pos = m.def_pos;
+    float* const s_r = m.r;
     for (int p = 0; p < B; ++p) {
         e->ucnt[(size_t)ui[2 * p]]++;
         e->icnt[(size_t)ui[2 * p + 1]]++;
@@ -747,49 +693,34 @@ int cf_pw_step(cf_pw* e, const int32_t* ui, const float* r, int32_t B, double* l
     }
     for (int p = 0; p < B; ++p) e->icnt[(size_t)s_ui[2 * p + 1]] = 0;
 
-    PW_HIP(hipMemcpyAsync(e->meta, m.data(), ((size_t)14 * B + 1) * 4, hipMemcpyHostToDevice, e->stream));
+    CF_HIP(hipMemcpyAsync(e->meta, e->h_meta.data(), pw_meta_words(B) * 4, hipMemcpyHostToDevice, e->stream));
+    const PwMeta dm = pw_meta(e->meta, B);
     PwArgs a{};
     a.d = e->d; a.Dp = e->Dp; a.B = B; a.kind = e->kind;
     a.s = e->s; a.reg = e->reg; a.lr = e->lr;
-    a.ui = e->meta;
-    a.r = reinterpret_cast<const float*>(e->meta + 2 * (size_t)B);
-    a.ustart = e->meta + 3 * (size_t)B;
-    a.ulen = a.ustart + B;
-    a.icnt = a.ulen + B;
-    a.def_row = a.icnt + B;
-    a.def_n = a.def_row + 2 * (size_t)B;
-    a.def_ptr = a.def_n + 2 * (size_t)B;
-    a.def_pos = a.def_ptr + 2 * (size_t)B + 1;
+    a.ui = dm.ui; a.r = dm.r;
+    a.ustart = dm.ustart; a.ulen = dm.ulen; a.icnt = dm.icnt;
+    a.def_row = dm.def_row; a.def_n = dm.def_n; a.def_ptr = dm.def_ptr; a.def_pos = dm.def_pos;
     a.n_def = nd; a.n_def_u = nd_u;
     a.U = e->U; a.AU = e->AU; a.V = e->V; a.AV = e->AV; a.K = e->K; a.AK = e->AK;
     a.part = e->part; a.kpart = e->kpart;
     a.tiles = tiles; a.tiles_per_block = tpb; a.blocks = blocks;
     a.loss_partial = e->loss_partial;
     a.loss_acc = e->loss_acc;
-    PW_HIP(launch_pw_grad(e, a));
-    PW_HIP(launch_pw_apply(e, a));
+    CF_HIP(launch_pw_grad(e, a));
+    CF_HIP(launch_pw_apply(e, a));
     if (svd) {
         hipLaunchKernelGGL(pw_kfold_kernel, dim3((e->d * e->d + kBlock - 1) / kBlock), dim3(kBlock), 0, e->stream, a);
-        PW_HIP(hipGetLastError());
+        CF_HIP(hipGetLastError());
     }
-    if (loss_out) {
-        PW_HIP(hipMemcpyAsync(e->h_loss.data(), e->loss_partial, (size_t)blocks * 8, hipMemcpyDeviceToHost,
-                              e->stream));
-        PW_HIP(hipStreamSynchronize(e->stream));
-        double t = 0.0;
-        for (int q = 0; q < blocks; ++q) t += e->h_loss[(size_t)q];
-        *loss_out = t;
-    }
+    if (loss_out) CF_TRY(cfi::read_loss(e->stream, e->loss_partial, blocks, e->h_loss, loss_out));
     return CF_OK;
 }
 
 int cf_pw_take_loss(cf_pw* e, double* sum_out) {
     if (!e || !sum_out) return cfi::set_error(CF_EINVAL, "null argument");
-    PW_HIP(hipSetDevice(e->device));
-    PW_HIP(hipMemcpyAsync(sum_out, e->loss_acc, 8, hipMemcpyDeviceToHost, e->stream));
-    PW_HIP(hipMemsetAsync(e->loss_acc, 0, 8, e->stream));
-    PW_HIP(hipStreamSynchronize(e->stream));
-    return CF_OK;
+    CF_HIP(hipSetDevice(e->device));
+    return cfi::take_loss(e->stream, e->loss_acc, sum_out);
 }
 
 int cf_pw_eval(cf_pw* e, const int32_t* ui, const float* r, int64_t n, float lo, float hi, float* pred_out,
@@ -804,17 +735,15 @@ int cf_pw_eval(cf_pw* e, const int32_t* ui, const float* r, int64_t n, float lo,
             return cfi::set_error(CF_EINVAL, "tuple " + std::to_string(p) + " out of range");
         if (!std::isfinite(r[p])) return cfi::set_error(CF_EINVAL, "rating " + std::to_string(p) + " is not finite");
     }
-    PW_HIP(hipSetDevice(e->device));
+    CF_HIP(hipSetDevice(e->device));
     const int64_t nb = (n + kPwEvalRows - 1) / kPwEvalRows;
-    int32_t* d_ui = nullptr;
-    float *d_r = nullptr, *d_pred = nullptr;
-    double* d_part = nullptr;
-    int rc;
-    if ((rc = palloc(&d_ui, (size_t)2 * n)) || (rc = palloc(&d_r, (size_t)n)) ||
-        (rc = palloc(&d_pred, (size_t)(pred_out ? n : 0))) || (rc = palloc(&d_part, (size_t)2 * nb))) {
-        pfree(d_ui); pfree(d_r); pfree(d_pred); pfree(d_part);
-        return rc;
-    }
+    cfi::DevBuf<int32_t> d_ui;
+    cfi::DevBuf<float> d_r, d_pred;
+    cfi::DevBuf<double> d_part;
+    CF_TRY(d_ui.reset((size_t)2 * n, "eval ui"));
+    CF_TRY(d_r.reset((size_t)n, "eval r"));
+    CF_TRY(d_pred.reset((size_t)(pred_out ? n : 0), "eval pred"));
+    CF_TRY(d_part.reset((size_t)2 * nb, "eval partials"));
     std::vector<double> h_part((size_t)2 * nb);
     hipError_t he = hipMemcpyAsync(d_ui, ui, (size_t)n * 8, hipMemcpyHostToDevice, e->stream);
     if (he == hipSuccess) he = hipMemcpyAsync(d_r, r, (size_t)n * 4, hipMemcpyHostToDevice, e->stream);
@@ -830,7 +759,6 @@ int cf_pw_eval(cf_pw* e, const int32_t* ui, const float* r, int64_t n, float lo,
     if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
     if (he == hipSuccess) he = hipMemcpy(h_part.data(), d_part, (size_t)2 * nb * 8, hipMemcpyDeviceToHost);
     if (he == hipSuccess && pred_out) he = hipMemcpy(pred_out, d_pred, (size_t)n * 4, hipMemcpyDeviceToHost);
-    pfree(d_ui); pfree(d_r); pfree(d_pred); pfree(d_part);
     if (he != hipSuccess) return cfi::set_error(CF_EHIP, std::string("cf_pw_eval: ") + hipGetErrorString(he));
     double t0 = 0.0, t1 = 0.0;
     for (int64_t b = 0; b < nb; ++b) {   // block order
@@ -844,63 +772,35 @@ int cf_pw_eval(cf_pw* e, const int32_t* ui, const float* r, int64_t n, float lo,
 
 int cf_pw_score_topk(cf_pw* e, const int32_t* users, int32_t n, int32_t k, int32_t exclude_train,
                      int32_t* idx_out, float* val_out) {
-    if (!e || n < 0 || !idx_out || (n > 0 && !users)) return cfi::set_error(CF_EINVAL, "bad arguments");
+    if (!e) return cfi::set_error(CF_EINVAL, "bad arguments");
     if (e->kind != CF_PW_MF)
         return cfi::set_error(CF_EINVAL, "cf_pw_score_topk serves the MF kind (svd.py has no recommend)");
-    if (k < 1 || k > 4096) return cfi::set_error(CF_EINVAL, "k must be 1..4096");
-    if (exclude_train && !e->indptr) return cfi::set_error(CF_ESTATE, "exclude_train needs cf_pw_set_interactions");
-    if (n == 0) return CF_OK;
-    for (int r = 0; r < n; ++r)
-        if (users[r] < 0 || users[r] >= e->n_users) return cfi::set_error(CF_EINVAL, "user id out of range");
-    PW_HIP(hipSetDevice(e->device));
+    CF_HIP(hipSetDevice(e->device));
     // wrmf.py:78-81, 98-111: U[test] V^T, top-k, train items dropped -- the rule of cf_score_topk
     const bool fused = k <= kFusedMaxWideK;
-    const size_t row_bytes = (size_t)e->n_items * 4;
-    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)256 << 20) / row_bytes));
-    uint32_t* keys = nullptr;
-    int32_t *d_users = nullptr, *d_idx = nullptr;
-    float* d_val = nullptr;
-    int rc;
-    if ((rc = palloc(&keys, fused ? 0 : (size_t)chunk * e->n_items)) || (rc = palloc(&d_users, (size_t)n)) ||
-        (rc = palloc(&d_idx, (size_t)n * k)) || (rc = palloc(&d_val, (size_t)n * k))) {
-        pfree(keys); pfree(d_users); pfree(d_idx); pfree(d_val);
-        return rc;
-    }
-    hipError_t he = hipMemcpyAsync(d_users, users, (size_t)n * 4, hipMemcpyHostToDevice, e->stream);
-    if (he == hipSuccess && fused) {
-        FusedTopkArgs f{};
-        f.model = CF_BPR;
-        f.d = e->d; f.Dp = (e->d + 7) & ~7; f.Dh = f.Dp / 2;
-        f.n_users = n; f.n_items = e->n_items; f.k = k;
-        f.users = d_users; f.U = e->U; f.V = e->V;
-        f.exclude_train = exclude_train ? 1 : 0;
-        f.indptr = e->indptr; f.indices = e->indices;
-        f.idx_out = d_idx; f.val_out = d_val;
-        he = launch_fused_topk(f, e->stream);
-    }
-    for (int u0 = 0; !fused && he == hipSuccess && u0 < n; u0 += chunk) {
-        const int m = std::min(chunk, n - u0);
-        ScoreArgs s{};
-        s.model = CF_BPR;
-        s.d = e->d; s.n_users = m; s.n_items = e->n_items;
-        s.users = d_users + u0; s.U = e->U; s.V = e->V;
-        s.keys = keys;
-        s.exclude_train = exclude_train ? 1 : 0;
-        s.indptr = e->indptr; s.indices = e->indices;
-        he = launch_score(s, e->stream);
-        if (he != hipSuccess) break;
-        TopkArgs t{};
-        t.k = k; t.n_items = e->n_items; t.keys = keys;
-        t.idx_out = d_idx + (size_t)u0 * k;
-        t.val_out = d_val + (size_t)u0 * k;
-        he = launch_topk(t, m, e->stream);
-    }
-    if (he == hipSuccess) he = hipStreamSynchronize(e->stream);
-    if (he == hipSuccess) he = hipMemcpy(idx_out, d_idx, (size_t)n * k * 4, hipMemcpyDeviceToHost);
-    if (he == hipSuccess && val_out) he = hipMemcpy(val_out, d_val, (size_t)n * k * 4, hipMemcpyDeviceToHost);
-    pfree(keys); pfree(d_users); pfree(d_idx); pfree(d_val);
-    if (he != hipSuccess) return cfi::set_error(CF_EHIP, std::string("cf_pw_score_topk: ") + hipGetErrorString(he));
-    return CF_OK;
+    return cfi::score_topk_chunks(
+        e->stream, "cf_pw", e->n_users, e->n_items, e->indptr != nullptr, users, n, k, exclude_train, idx_out,
+        val_out, !fused, [&](const int32_t* d_users, int m, uint32_t* keys, int32_t* d_idx, float* d_val) {
+            if (fused) {   // all n users, straight to d_idx / d_val
+                FusedTopkArgs f{};
+                f.model = CF_BPR;
+                f.d = e->d; f.Dp = (e->d + 7) & ~7; f.Dh = f.Dp / 2;
+                f.n_users = m; f.n_items = e->n_items; f.k = k;
+                f.users = d_users; f.U = e->U; f.V = e->V;
+                f.exclude_train = exclude_train ? 1 : 0;
+                f.indptr = e->indptr; f.indices = e->indices;
+                f.idx_out = d_idx; f.val_out = d_val;
+                return launch_fused_topk(f, e->stream);
+            }
+            ScoreArgs s{};
+            s.model = CF_BPR;
+            s.d = e->d; s.n_users = m; s.n_items = e->n_items;
+            s.users = d_users; s.U = e->U; s.V = e->V;
+            s.keys = keys;
+            s.exclude_train = exclude_train ? 1 : 0;
+            s.indptr = e->indptr; s.indices = e->indices;
+            return launch_score(s, e->stream);
+        });
 }
 
 }  // extern "C"

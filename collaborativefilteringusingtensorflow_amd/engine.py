@@ -10,10 +10,7 @@ import ctypes
 import numpy as np
 
 from . import _native as N
-
-
-def _ptr(a, ctype):
-    return a.ctypes.data_as(ctypes.POINTER(ctype))
+from ._native import _ptr
 
 
 def _i32(a):

@@ -20,6 +20,7 @@ import time
 import numpy as np
 
 from . import _native as N
+from ._native import _ptr
 from ._model import parse_device
 from .io_util import to_csr
 from .ranking import evaluateCV, evaluateLOOV
@@ -27,35 +28,18 @@ from .ranking import evaluateCV, evaluateLOOV
 TABLES = {"user": 0, "item": 1, "h": 2, "acc_user": 3, "acc_item": 4, "acc_h": 5}
 
 
-def _ptr(a, ctype):
-    return a.ctypes.data_as(ctypes.POINTER(ctype))
-
-
-class EnsembleEngine(object):
+class EnsembleEngine(N._NativeObject):
     """One HIP device's ensemble tables U [K, n_users, d], V [K, n_items, d],
     H [K, d] and their Adagrad accumulators."""
 
+    PREFIX, TABLES = "cf_ens", TABLES
+
     def __init__(self, n_users, n_items, kensemble, n_factors, reg=0.1, lr=0.1, acc_init=0.1,
                  device=0):
-        L = N.lib()
-        self._L = L
         self.n_users, self.n_items = int(n_users), int(n_items)
         self.K, self.d = int(kensemble), int(n_factors)
-        self._h = ctypes.c_void_p()
-        N.check(L.cf_ens_create(self.n_users, self.n_items, self.K, self.d, float(reg), float(lr),
-                                float(acc_init), int(device), ctypes.byref(self._h)),
-                "cf_ens_create")
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._L.cf_ens_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(self.n_users, self.n_items, self.K, self.d, float(reg), float(lr), float(acc_init),
+                     int(device))
 
     def _shape(self, name):
         t = TABLES[name] % 3
@@ -67,26 +51,6 @@ class EnsembleEngine(object):
 
     def set_lr(self, lr):
         N.check(self._L.cf_ens_set_lr(self._h, float(lr)), "cf_ens_set_lr")
-
-    def set_table(self, name, arr):
-        a = np.ascontiguousarray(arr, dtype=np.float32)
-        if a.shape != self._shape(name):
-            raise ValueError("%s must be %s, got %s" % (name, self._shape(name), a.shape))
-        N.check(self._L.cf_ens_set_table(self._h, TABLES[name], _ptr(a, ctypes.c_float), a.size),
-                "cf_ens_set_table")
-
-    def get_table(self, name):
-        a = np.empty(self._shape(name), dtype=np.float32)
-        N.check(self._L.cf_ens_get_table(self._h, TABLES[name], _ptr(a, ctypes.c_float), a.size),
-                "cf_ens_get_table")
-        return a
-
-    def set_interactions(self, indptr, indices):
-        ip = np.ascontiguousarray(indptr, dtype=np.int64)
-        ix = np.ascontiguousarray(indices, dtype=np.int32)
-        N.check(self._L.cf_ens_set_interactions(self._h, _ptr(ip, ctypes.c_int64),
-                                                _ptr(ix, ctypes.c_int32), ix.shape[0]),
-                "cf_ens_set_interactions")
 
     def step(self, uij, return_loss=True):
         t = np.ascontiguousarray(uij, dtype=np.int32)
@@ -109,20 +73,8 @@ class EnsembleEngine(object):
                                       ctypes.byref(loss) if return_loss else None), "cf_ens_step_w")
         return float(loss.value) if return_loss else None
 
-    def take_loss(self):
-        s = ctypes.c_double(0.0)
-        N.check(self._L.cf_ens_take_loss(self._h, ctypes.byref(s)), "cf_ens_take_loss")
-        return float(s.value)
-
     def score_topk(self, users, k, exclude_train=True, return_values=False):
-        u = np.ascontiguousarray(users, dtype=np.int32)
-        idx = np.empty((u.shape[0], int(k)), dtype=np.int32)
-        val = np.empty((u.shape[0], int(k)), dtype=np.float32) if return_values else None
-        N.check(self._L.cf_ens_score_topk(self._h, _ptr(u, ctypes.c_int32), u.shape[0], int(k),
-                                          int(bool(exclude_train)), _ptr(idx, ctypes.c_int32),
-                                          _ptr(val, ctypes.c_float) if val is not None else None),
-                "cf_ens_score_topk")
-        return (idx, val) if return_values else idx
+        return self._score_topk(users, k, exclude_train, return_values)
 
 
 class Ensemble(object):

@@ -26,6 +26,7 @@ import time
 import numpy as np
 
 from . import _native as N
+from ._native import _ptr
 from ._model import parse_device
 from .io_util import to_csr
 from .ranking import evaluateCV, evaluateLOOV
@@ -33,35 +34,18 @@ from .ranking import evaluateCV, evaluateLOOV
 TABLES = {"user": 0, "item": 1, "key": 2, "memory": 3, "acc_user": 4, "acc_item": 5}
 
 
-def _ptr(a, ctype):
-    return a.ctypes.data_as(ctypes.POINTER(ctype))
-
-
-class LRMLEngine(object):
+class LRMLEngine(N._NativeObject):
     """One HIP device's LRML tables U [n_users, d], V [n_items, d], Key [d, M],
     Mem [M, d] and the Adagrad accumulators of U and V."""
 
+    PREFIX, TABLES = "cf_lrml", TABLES
+
     def __init__(self, n_users, n_items, n_factors=50, n_memory=20, margin=0.2, clip_norm=1.0,
                  lr=0.01, acc_init=0.1, device=0):
-        L = N.lib()
-        self._L = L
         self.n_users, self.n_items = int(n_users), int(n_items)
         self.d, self.M = int(n_factors), int(n_memory)
-        self._h = ctypes.c_void_p()
-        N.check(L.cf_lrml_create(self.n_users, self.n_items, self.d, self.M, float(margin),
-                                 float(clip_norm), float(lr), float(acc_init), int(device),
-                                 ctypes.byref(self._h)), "cf_lrml_create")
-
-    def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            self._L.cf_lrml_destroy(self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._create(self.n_users, self.n_items, self.d, self.M, float(margin), float(clip_norm), float(lr),
+                     float(acc_init), int(device))
 
     def _shape(self, name):
         return {"user": (self.n_users, self.d), "item": (self.n_items, self.d),
@@ -71,26 +55,6 @@ class LRMLEngine(object):
     def init_params(self, mean=0.0, stddev=0.01, seed=1):
         N.check(self._L.cf_lrml_init_params(self._h, float(mean), float(stddev),
                                             int(seed) & 0xFFFFFFFFFFFFFFFF), "cf_lrml_init_params")
-
-    def set_table(self, name, arr):
-        a = np.ascontiguousarray(arr, dtype=np.float32)
-        if a.shape != self._shape(name):
-            raise ValueError("%s must be %s, got %s" % (name, self._shape(name), a.shape))
-        N.check(self._L.cf_lrml_set_table(self._h, TABLES[name], _ptr(a, ctypes.c_float), a.size),
-                "cf_lrml_set_table")
-
-    def get_table(self, name):
-        a = np.empty(self._shape(name), dtype=np.float32)
-        N.check(self._L.cf_lrml_get_table(self._h, TABLES[name], _ptr(a, ctypes.c_float), a.size),
-                "cf_lrml_get_table")
-        return a
-
-    def set_interactions(self, indptr, indices):
-        ip = np.ascontiguousarray(indptr, dtype=np.int64)
-        ix = np.ascontiguousarray(indices, dtype=np.int32)
-        N.check(self._L.cf_lrml_set_interactions(self._h, _ptr(ip, ctypes.c_int64),
-                                                 _ptr(ix, ctypes.c_int32), ix.shape[0]),
-                "cf_lrml_set_interactions")
 
     def step(self, pos, neg, return_loss=True):
         p = np.ascontiguousarray(pos, dtype=np.int32)
@@ -103,23 +67,10 @@ class LRMLEngine(object):
                 "cf_lrml_step")
         return float(loss.value) if return_loss else None
 
-    def take_loss(self):
-        s = ctypes.c_double(0.0)
-        N.check(self._L.cf_lrml_take_loss(self._h, ctypes.byref(s)), "cf_lrml_take_loss")
-        return float(s.value)
-
     def score_topk(self, users, k, exclude_train=True, predict_mode="reference", return_values=False):
         if predict_mode not in N.LRML_MODES:
             raise ValueError("predict_mode must be one of %s" % sorted(N.LRML_MODES))
-        u = np.ascontiguousarray(users, dtype=np.int32)
-        idx = np.empty((u.shape[0], int(k)), dtype=np.int32)
-        val = np.empty((u.shape[0], int(k)), dtype=np.float32) if return_values else None
-        N.check(self._L.cf_lrml_score_topk(self._h, _ptr(u, ctypes.c_int32), u.shape[0], int(k),
-                                           int(bool(exclude_train)), N.LRML_MODES[predict_mode],
-                                           _ptr(idx, ctypes.c_int32),
-                                           _ptr(val, ctypes.c_float) if val is not None else None),
-                "cf_lrml_score_topk")
-        return (idx, val) if return_values else idx
+        return self._score_topk(users, k, exclude_train, return_values, N.LRML_MODES[predict_mode])
 
 
 class LRML(object):

@@ -671,10 +671,11 @@ int cf_profile_enable(cf_engine* eng, int32_t on);
 int cf_profile_read(cf_engine* eng, int32_t kernel_id,
                     double* total_ms_out, int64_t* launches_out);
 int cf_profile_reset(cf_engine* eng);
-/* Bytes of device and of pinned host memory that the engines of this process
- * hold right now (every engine-owned buffer, on every device; caller memory
- * bound to an engine is not counted).  Either output may be NULL.  Equal
- * values before cf_create and after cf_destroy mean nothing leaked. */
+/* Bytes of device and of pinned host memory that the objects of this process
+ * hold right now: every buffer owned by an engine or by an ensemble, LRML or
+ * pointwise object, on every device; caller memory bound to an engine is not
+ * counted.  Either output may be NULL.  Equal values before a create and
+ * after its destroy mean nothing leaked. */
 int cf_debug_live_bytes(int64_t* device_bytes, int64_t* pinned_bytes);
 
 /* ---- rating-file ingest ----------------------------------

@@ -18,8 +18,11 @@ pytestmark = pytest.mark.gpu
 # elementwise: |gpu - oracle| <= 4e-5 + 1e-4 |oracle| (the former max-relative 1e-4 at max|ref| ~ 0.4
 # allowed 4e-5 on every element; the [B, B] ensemble loss sums B^2 terms in fp32)
 RTOL, ATOL = 1e-4, 4e-5
-
-
+# (indptr, indices) that no object takes, at n_users = 3, n_items = 4
+BAD_CSR = [([0, 1, 2, 2], [0, 1, 2]),   # indptr does not span nnz = 3
+           ([0, 2, 1, 3], [0, 1, 2]),   # indptr not monotone
+           ([0, 2, 2, 2], [2, 1]),      # an unsorted row
+           ([0, 1, 1, 1], [4])]         # item id 4
 
 
 def make(K, nu, ni, d, reg, seed=5):
@@ -104,6 +107,33 @@ def test_ensemble_rejects_bad_ids():
         e.step(np.array([[0, 1, 20]]))
     with pytest.raises(N.NativeError, match="exclude_train"):
         e.score_topk(np.array([0]), 5, exclude_train=True)
+    e.close()
+
+
+def test_ensemble_rejects_bad_csr():
+    """A CSR that does not span nnz, is not monotone, holds an unsorted row or
+    an item past n_items is CF_EINVAL, and is not installed."""
+    from collaborativefilteringusingtensorflow_amd import _native as N
+    e, *_ = make(1, 3, 4, 1, 0.1)
+    for indptr, indices in BAD_CSR:
+        with pytest.raises(N.NativeError, match="CF_EINVAL"):
+            e.set_interactions(indptr, indices)
+    with pytest.raises(N.NativeError, match="exclude_train"):
+        e.score_topk(np.array([0]), 2, exclude_train=True)
+    e.close()
+
+
+def test_ensemble_recommend_chunks_past_grid_y():
+    """65,537 users in one call: more than one launch's grid.y (65,535).  The
+    lists equal those of two calls that each fit, bit for bit."""
+    nu = 65537
+    e, *_ = make(1, nu, 8, 4, 0.1)
+    users = np.arange(nu, dtype=np.int32)
+    idx, val = e.score_topk(users, 2, exclude_train=False, return_values=True)
+    ia, va = e.score_topk(users[:40000], 2, exclude_train=False, return_values=True)
+    ib, vb = e.score_topk(users[40000:], 2, exclude_train=False, return_values=True)
+    assert np.array_equal(idx, np.concatenate([ia, ib]))
+    assert np.array_equal(val.view(np.uint32), np.concatenate([va, vb]).view(np.uint32))
     e.close()
 
 

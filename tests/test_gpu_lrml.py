@@ -197,6 +197,18 @@ def test_lrml_recommend_key_block_tail(mode):
     e.close()
 
 
+def test_lrml_rejects_bad_csr():
+    from collaborativefilteringusingtensorflow_amd import _native as N
+    from test_gpu_ensemble import BAD_CSR
+    e = make(C.init_tables(1, 3, 4, 1, 1, 0.1), 3, 4)
+    for indptr, indices in BAD_CSR:
+        with pytest.raises(N.NativeError, match="CF_EINVAL"):
+            e.set_interactions(indptr, indices)
+    with pytest.raises(N.NativeError, match="exclude_train"):   # none of them was installed
+        e.score_topk(np.array([0]), 2, exclude_train=True)
+    e.close()
+
+
 def test_lrml_rejects_bad_ids():
     from collaborativefilteringusingtensorflow_amd import _native as N
     tabs = C.init_tables(1, 10, 20, 8, 4, 0.1)

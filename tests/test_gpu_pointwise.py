@@ -226,6 +226,18 @@ def test_wrmf_recommend_fold1(fold1, trained):
     e.close()
 
 
+def test_pointwise_rejects_bad_csr():
+    from collaborativefilteringusingtensorflow_amd import _native as N
+    from test_gpu_ensemble import BAD_CSR
+    e = make("mf", C.init_tables("mf", 1, 3, 4, 1), 3, 4)
+    for indptr, indices in BAD_CSR:
+        with pytest.raises(N.NativeError, match="CF_EINVAL"):
+            e.set_interactions(indptr, indices)
+    with pytest.raises(N.NativeError, match="exclude_train"):   # none of them was installed
+        e.score_topk(np.array([0]), 2, exclude_train=True)
+    e.close()
+
+
 @pytest.mark.parametrize("kind", ["mf", "svd"])
 def test_bad_inputs_leave_the_tables_untouched(kind):
     from collaborativefilteringusingtensorflow_amd import _native as N
