@@ -21,6 +21,20 @@ __device__ __forceinline__ uint64_t uniform_below(uint64_t h, uint64_t n) {
     return __umul64hi(h, n);
 }
 
+// The sampler's draws, shared by the step's draw (prep_body) and the epoch
+// pass that writes the negatives into the records (cf_epoch.hip): an epoch's
+// key, the key of the pair at position `slot` of the epoch's order, and
+// attempt `ctr` of that pair's sequence of candidates.
+__host__ __device__ __forceinline__ uint64_t draw_rng_key(uint64_t seed, uint64_t epoch) {
+    return mix64(seed ^ mix64(epoch * 0x9E3779B97F4A7C15ull + 0x2545F4914F6CDD1Dull));
+}
+__host__ __device__ __forceinline__ uint64_t draw_pair_key(uint64_t rng_key, uint64_t slot) {
+    return mix64(rng_key ^ (slot * 0xD1B54A32D192ED03ull));
+}
+__device__ __forceinline__ int32_t draw_item(uint64_t key, uint64_t ctr, int64_t n_items) {
+    return (int32_t)uniform_below(mix64(key + ctr), (uint64_t)n_items);
+}
+
 // One bijective pass on [0, 2^bits): xor key, multiply by odd, xorshift.
 __host__ __device__ __forceinline__ uint64_t perm_rounds(uint64_t x, const PermKey& p) {
 #pragma unroll

@@ -103,6 +103,11 @@ struct cf_engine {
     // the batch's user runs (StepArgs::user_runs); 0 (default) = one returning
     // count atomic per pair -- the runs measured even at cfg2 (prep_body)
     int user_runs = 0;
+    // cf_set_option("neg_records"): 0 off, 1 on, 2 auto (the default; as 1).
+    // Where it applies (neg_records_on) the epoch pass draws each pair's
+    // negative and the records leave as (u, i, j, 0): the step's draw is the
+    // record's load and its counts (StepArgs::neg_recs)
+    int neg_records = 2;
     struct EpochOrder {
         DevBuf<int32_t> keys;        // radix-sort path: [2 nnz]
         DevBuf<int32_t> vals;        // index form: [nnz] (counting) or [2 nnz] (radix sort)
@@ -113,6 +118,7 @@ struct cf_engine {
         DevBuf<int4> recs;           // records form (sorted_batches 1 / 2): the sorted pair records
         const int4* recs_sorted = nullptr;
         bool with_recs = false;
+        bool with_negs = false;      // the records are (u, i, j, 0) (neg_records)
         hipEvent_t ready = nullptr;
         bool async = false;          // computed on eo_stream: the engine stream waits on `ready`
     } eo[2];
@@ -720,6 +726,18 @@ bool sorted_batches_on(const cf_engine* e, int B) {
     return e->sorted_batches == 1 || e->sorted_batches == 3 || e->nnz / B >= kSortedAutoBatches;
 }
 
+// The records carry their negatives (cf_set_option "neg_records") where the
+// counting scatter writes the records form, every pair has one negative and no
+// group users, and the draw is the plain row scan: W > 1 would need 32-B
+// records, the set probe / speculative counts / user runs are draws of their own
+bool neg_records_on(const cf_engine* e, int B) {
+    const cf_config& c = e->cfg;
+    if (e->neg_records == 0 || !e->pairs || !sorted_batches_on(e, B) || e->sorted_batches == 3) return false;
+    if (e->epoch_sort != 0 || !epoch_count_ok(e->nnz, B)) return false;
+    if (c.model == CF_PLR || c.n_neg != 1 || group_count(c) != 0) return false;
+    return !e->neg_check && !e->spec_neg && !e->user_runs;
+}
+
 // the epoch order's buffers for (nnz, B) and the option values: the counting
 // scatter (cf_epoch.hip) writes the result once (records: int4[nnz], index
 // form: int32[nnz]) and takes a small histogram scratch; the radix sort
@@ -807,11 +825,14 @@ int compute_epoch_order(cf_engine* e, int k, int64_t epoch, int B, hipStream_t s
     CF_TRY(refit(o.recs, (size_t)n.recs, "epoch order records"));
     CF_TRY(refit(o.tmp, n.tmp, "epoch order scratch"));
     const PermKey pk = make_perm_key((uint64_t)nnz, e->cfg.seed, (uint64_t)epoch);
+    const bool wn = neg_records_on(e, B);   // (implies wr and n.counting)
+    // the negatives of the epoch being ordered: the next one when this runs ahead
+    const EpochNeg neg{e->indices.p, e->cfg.n_items, draw_rng_key_host(e->cfg.seed, (uint64_t)epoch)};
     {
         ProfScope ps(e, CF_K_EPOCH_ORDER, st);
         if (n.counting) {
             CF_HIP(launch_epoch_count(pk, nnz, B, wr ? e->pairs.p : nullptr, wr ? o.recs.p : nullptr,
-                                      wr ? nullptr : o.vals.p, o.tmp, o.tmp.cap, st));
+                                      wr ? nullptr : o.vals.p, o.tmp, o.tmp.cap, st, wn ? &neg : nullptr));
             o.recs_sorted = wr ? o.recs.p : nullptr;
             o.order = wr ? nullptr : o.vals.p;
         } else if (wr) {
@@ -822,6 +843,7 @@ int compute_epoch_order(cf_engine* e, int k, int64_t epoch, int B, hipStream_t s
             o.recs_sorted = nullptr;
         }
         o.with_recs = wr;
+        o.with_negs = wn;
     }
     o.epoch = epoch;
     o.B = B;
@@ -832,7 +854,7 @@ int compute_epoch_order(cf_engine* e, int k, int64_t epoch, int B, hipStream_t s
 
 // the order of the sampler's epoch at batch size B, ready on the engine
 // stream; the next epoch's is started on eo_stream
-int epoch_order(cf_engine* e, int B, const int32_t** out, const int4** recs_out) {
+int epoch_order(cf_engine* e, int B, const int32_t** out, const int4** recs_out, int* negs_out) {
     if (!e->eo_stream) {
         int lo = 0, hi = 0;
         CF_HIP(hipDeviceGetStreamPriorityRange(&lo, &hi));
@@ -842,7 +864,10 @@ int epoch_order(cf_engine* e, int B, const int32_t** out, const int4** recs_out)
     }
     const int64_t ep = e->epoch;
     const bool wr = e->sorted_batches != 3;
-    auto have = [&](const cf_engine::EpochOrder& o, int64_t epc) { return o.epoch == epc && o.B == B && o.with_recs == wr; };
+    const bool wn = neg_records_on(e, B);
+    auto have = [&](const cf_engine::EpochOrder& o, int64_t epc) {
+        return o.epoch == epc && o.B == B && o.with_recs == wr && o.with_negs == wn;
+    };
     int k = have(e->eo[0], ep) ? 0 : have(e->eo[1], ep) ? 1 : -1;
     if (k < 0) {
         // not computed ahead (first epoch, a jump, another B): in order on the engine stream
@@ -863,6 +888,7 @@ int epoch_order(cf_engine* e, int B, const int32_t** out, const int4** recs_out)
     }
     *out = e->eo[k].order;
     *recs_out = e->eo[k].with_recs ? e->eo[k].recs_sorted : nullptr;
+    *negs_out = e->eo[k].with_recs && e->eo[k].with_negs ? 1 : 0;
     cf_engine::EpochOrder& nx = e->eo[k ^ 1];
     if (!have(nx, ep + 1) && e->nnz / B >= 2) {
         // the next epoch's order, behind everything the engine stream holds
@@ -900,21 +926,23 @@ int sampler_args(cf_engine* e, int B, StepArgs* a) {
     a->sample = 1;
     a->slot_base = (uint64_t)(e->batch * (int64_t)B);
     a->perm = make_perm_key((uint64_t)e->nnz, e->cfg.seed, (uint64_t)e->epoch);
-    a->rng_key = mix64_host(e->cfg.seed ^ mix64_host((uint64_t)e->epoch * 0x9E3779B97F4A7C15ull +
-                                                     0x2545F4914F6CDD1Dull));
+    a->rng_key = draw_rng_key_host(e->cfg.seed, (uint64_t)e->epoch);
     if (sorted_batches_on(e, B) && e->sorted_batches == 2 && !sorted_auto_fits(e, B)) e->sorted_auto_off = true;
     if (sorted_batches_on(e, B)) {
         const int32_t* ord = nullptr;
         const int4* recs = nullptr;
-        const int rc = epoch_order(e, B, &ord, &recs);
+        int negs = 0;
+        const int rc = epoch_order(e, B, &ord, &recs, &negs);
         if (rc == CF_ENOMEM && e->sorted_batches == 2) {
             free_epoch_orders(e);   // auto: unsorted batches from here on
+            (void)hipGetLastError();   // the failed allocation's error is handled here
             e->sorted_auto_off = true;
         } else if (rc != CF_OK) {
             return rc;
         } else {
             a->order = ord;   // batch b's pairs at [bB, bB + B), CSR order
             a->order_recs = recs;
+            a->neg_recs = negs;
             a->user_runs = e->user_runs && group_count(e->cfg) == 0 ? 1 : 0;
         }
     }
@@ -3011,6 +3039,12 @@ int cf_set_option(cf_engine* e, const char* name, int64_t value) {
         e->user_runs = (int)value;
         return CF_OK;
     }
+    if (n == "neg_records") {   // the epoch pass draws the negatives into the records (neg_records_on)
+        if (value < 0 || value > 2) return fail(CF_EINVAL, "neg_records must be 0, 1 or 2");
+        CF_TRY(discard_pending(e));
+        e->neg_records = (int)value;   // a cached order in the other form is recomputed (epoch_order's have)
+        return CF_OK;
+    }
     if (n == "epoch_sort") {   // how the sorted batches' epoch order is formed (epoch_need)
         if (value < 0 || value > 1) return fail(CF_EINVAL, "epoch_sort must be 0 or 1");
         CF_TRY(discard_pending(e));
@@ -3182,6 +3216,7 @@ int cf_step_path(cf_engine* e, int32_t B, int32_t* flags_out) {
     if (e->det) f |= CF_PATH_DETERMINISTIC;
     if (c.dense_item_apply) f |= CF_PATH_DENSE_ITEMS;
     if (e->pairs && sorted_batches_on(e, B)) f |= CF_PATH_SORTED_BATCHES;
+    if (neg_records_on(e, B)) f |= CF_PATH_NEG_RECORDS;
     f |= (e->pipeline & 3) << 8;
     *flags_out = f;
     return CF_OK;

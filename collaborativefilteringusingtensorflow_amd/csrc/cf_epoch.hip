@@ -29,6 +29,10 @@
 // kEpochMaxBins bins and as cf_set_option("epoch_sort", 1)), without its key
 // arrays: HBM traffic per pair = 2 B bin written + read, 16 B record read,
 // 16 B record written (records form; 4 B index written in the index form).
+//
+// With an EpochNeg (cf_set_option "neg_records") pass 3 also draws each
+// pair's W = 1 negative and writes the record as (u, i, j, 0): the step's
+// draw then only loads and counts it (prep_recs_body, cf_kernels_impl.h).
 #include "cf_kernels.h"
 #include "cf_device.h"
 
@@ -177,12 +181,22 @@ __device__ __forceinline__ int32_t block_excl_scan(int32_t v, int32_t* wtot) {
 // the index form (profiles/r06/r06c) -- 44 KB of LDS per block (3 blocks per
 // CU) and random 16-B LDS writes; the copy-out gathers each record from the
 // tile's 32 KB instead, whose lines the block's other lanes read too (L2)
-template <bool RECS>
+//
+// NEG (records form): the record headed to position g leaves as (u, i, j, 0),
+// j the negative the step's draw takes at slot g (prep_body, W = 1): the first
+// attempt k = 0, 1, .. of draw_item(draw_pair_key(rng_key, g), k) that is not
+// in the user's sorted row indices[rb, rb + len) -- the tile's own 8 KB of
+// `indices` and its neighbours', so the probes hit L1 / L2 where the step
+// fetched the row from a random place in HBM.  A thread tests the first
+// attempts of its eight records in lock-step, one binary-search probe of each
+// per round (eight independent loads in flight); a rejected first attempt
+// (|Pos(u)| / n_items of them) walks on by itself with sorted_contains.
+template <bool RECS, bool NEG = false>
 __global__ void __launch_bounds__(kBlock) epoch_scatter_kernel(EpochCtx c, const uint16_t* __restrict__ bins,
                                                                const int32_t* __restrict__ off,
                                                                const int4* __restrict__ pairs,
                                                                int4* __restrict__ out_recs,
-                                                               int32_t* __restrict__ out_idx) {
+                                                               int32_t* __restrict__ out_idx, EpochNeg neg) {
     extern __shared__ int32_t lds[];
     const int nbn = c.n_bins;
     int32_t* stage = lds;                        // [kEpochTile] pair index of each tile position
@@ -284,6 +298,50 @@ __global__ void __launch_bounds__(kBlock) epoch_scatter_kernel(EpochCtx c, const
             g[i] = gstage[Lc];
             r[i] = pairs[stage[Lc]];
         }
+        if constexpr (NEG) {
+            const int32_t* __restrict__ ind = neg.indices;
+            int32_t j[kEpochItems];
+            uint32_t found = 0;
+#pragma unroll
+            for (int i = 0; i < kEpochItems; ++i)
+                j[i] = draw_item(draw_pair_key(neg.rng_key, (uint64_t)(uint32_t)g[i]), 0, neg.n_items);
+            // binary search in [r.z, r.z + r.w), narrowed in place; an equal
+            // id is always probed before the range is empty
+            bool more = true;
+            while (more) {
+                more = false;
+#pragma unroll
+                for (int i = 0; i < kEpochItems; ++i) {
+                    if (r[i].w > 0) {
+                        const int32_t half = r[i].w >> 1;
+                        const int32_t v = ind[(uint32_t)r[i].z + (uint32_t)half];
+                        if (v < j[i]) {
+                            r[i].z += half + 1;
+                            r[i].w -= half + 1;
+                        } else {
+                            r[i].w = v == j[i] ? 0 : half;
+                        }
+                        found |= v == j[i] ? 1u << i : 0u;
+                        more |= r[i].w > 0;
+                    }
+                }
+            }
+#pragma unroll
+            for (int i = 0; i < kEpochItems; ++i) {
+                if ((found >> i) & 1u) {   // rare: the record again for its row, then attempt 1, 2, ..
+                    const int L = tid + i * kBlock;
+                    const int4 q = pairs[stage[L < tile_len ? L : 0]];
+                    const int64_t rb = (int64_t)(uint32_t)q.z, re = rb + q.w;
+                    const uint64_t key = draw_pair_key(neg.rng_key, (uint64_t)(uint32_t)g[i]);
+                    uint64_t k = 1;
+                    do {
+                        j[i] = draw_item(key, k++, neg.n_items);
+                    } while (sorted_contains(ind, rb, re, j[i]));
+                }
+                r[i].z = j[i];
+                r[i].w = 0;
+            }
+        }
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int i = 0; i < kEpochItems; ++i) out_recs[g[i]] = r[i];
@@ -342,9 +400,11 @@ size_t epoch_count_scratch(int64_t nnz, int B) {
 }
 
 hipError_t launch_epoch_count(const PermKey& p, int64_t nnz, int B, const int4* pairs, int4* out_recs,
-                              int32_t* out_idx, void* tmp, size_t tmp_bytes, hipStream_t s) {
+                              int32_t* out_idx, void* tmp, size_t tmp_bytes, hipStream_t s, const EpochNeg* neg) {
     if (!epoch_count_ok(nnz, B) || (uint64_t)nnz != p.n || p.mask > 0xFFFFFFFFull) return hipErrorInvalidValue;
     if ((pairs == nullptr) != (out_recs == nullptr) || (out_recs == nullptr) == (out_idx == nullptr))
+        return hipErrorInvalidValue;
+    if (neg != nullptr && (out_recs == nullptr || neg->indices == nullptr || neg->n_items < 1))
         return hipErrorInvalidValue;
     if (tmp_bytes < epoch_count_scratch(nnz, B)) return hipErrorInvalidValue;
     const EpochCtx c = epoch_ctx(p, nnz, B);
@@ -364,12 +424,15 @@ hipError_t launch_epoch_count(const PermKey& p, int64_t nnz, int B, const int4* 
                   (size_t)(2 * kEpochTile + kWavesPerBlock) * sizeof(int32_t);
     // (fewer blocks per CU -- LDS padded to 40 / 54 / 80 KB -- measured
     // slower: records 0.72 / 0.75 / 0.75 vs 0.70 ms, profiles/r06/r06g)
-    if (out_recs)
-        hipLaunchKernelGGL(epoch_scatter_kernel<true>, grid, dim3(kBlock), lds3, s, c, bins, cnt, pairs, out_recs,
-                           nullptr);
+    if (neg)
+        hipLaunchKernelGGL((epoch_scatter_kernel<true, true>), grid, dim3(kBlock), lds3, s, c, bins, cnt, pairs,
+                           out_recs, nullptr, *neg);
+    else if (out_recs)
+        hipLaunchKernelGGL((epoch_scatter_kernel<true>), grid, dim3(kBlock), lds3, s, c, bins, cnt, pairs, out_recs,
+                           nullptr, EpochNeg{});
     else
-        hipLaunchKernelGGL(epoch_scatter_kernel<false>, grid, dim3(kBlock), lds3, s, c, bins, cnt, nullptr, nullptr,
-                           out_idx);
+        hipLaunchKernelGGL((epoch_scatter_kernel<false>), grid, dim3(kBlock), lds3, s, c, bins, cnt, nullptr, nullptr,
+                           out_idx, EpochNeg{});
     return hipGetLastError();
 }
 

@@ -92,6 +92,11 @@ struct StepArgs {
     // the draw takes user ranks and counts from the runs (prep_body) instead
     // of one returning count atomic per pair
     int user_runs;
+    // the records carry their negatives (cf_set_option "neg_records"; W = 1,
+    // no group users): order_recs[slot] = (u, i, j, 0), j drawn by the epoch
+    // pass (launch_epoch_count) with this epoch's rng_key and the slot's key,
+    // so the draw is the record's load and its three counts (prep_recs_body)
+    int neg_recs;
     // deterministic mode on the positive-sorted path (round 3):
     // every sum of gradient rows is taken in 64-bit fixed point (kFxOne
     // units), which is associative, so the result does not depend on the
@@ -519,12 +524,22 @@ hipError_t launch_epoch_records(const PermKey& p, int64_t nnz, int B, const int4
 // the same orders as one hand-written counting sort by batch id
 // (cf_epoch.hip), for nnz <= 2^31 and at most kEpochMaxBins = nnz / B + 1
 // bins: out_recs[nnz] (records form, pairs != null) or out_idx[nnz] (index
-// form), bitwise the stable radix sort's result
+// form), bitwise the stable radix sort's result.  With `neg` (records form
+// only) the record at output position g leaves as (u, i, j, 0), j the W = 1
+// negative the step's draw would take at slot g of this epoch: the first
+// attempt of draw_item(draw_pair_key(neg->rng_key, g), k), k = 0, 1, ..
+// outside the user's sorted row of neg->indices (StepArgs::neg_recs)
 constexpr int kEpochMaxBins = 1024;
+struct EpochNeg {
+    const int32_t* indices;   // [nnz] sorted per user (the rows the records point into)
+    int64_t n_items;
+    uint64_t rng_key;         // draw_rng_key(seed, the epoch being ordered)
+};
 bool epoch_count_ok(int64_t nnz, int B);
 size_t epoch_count_scratch(int64_t nnz, int B);
 hipError_t launch_epoch_count(const PermKey& p, int64_t nnz, int B, const int4* pairs, int4* out_recs,
-                              int32_t* out_idx, void* tmp, size_t tmp_bytes, hipStream_t s);
+                              int32_t* out_idx, void* tmp, size_t tmp_bytes, hipStream_t s,
+                              const EpochNeg* neg = nullptr);
 // a discarded draw's phantoms (StepArgs::spec_ph): uncount them, re-zero spec_n
 hipError_t launch_uncount_spec(const int2* ph, int* n, int32_t* cnt, hipStream_t s);
 hipError_t launch_build_pos_set(const int4* pairs, int64_t nnz, unsigned long long* set,
@@ -545,5 +560,7 @@ hipError_t launch_xchg_accumulate(const int32_t* ids, int64_t n, int64_t u0, con
 // host-side mirror of the device bijection (for key generation)
 PermKey make_perm_key(uint64_t n, uint64_t seed, uint64_t epoch);
 uint64_t mix64_host(uint64_t z);
+// the draw key of an epoch (draw_rng_key, cf_device.h)
+uint64_t draw_rng_key_host(uint64_t seed, uint64_t epoch);
 
 }  // namespace cfk

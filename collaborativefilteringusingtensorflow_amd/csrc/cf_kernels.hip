@@ -534,6 +534,7 @@ hipError_t launch_pack_batch(const PackArgs& a, hipStream_t s) {
 }
 
 uint64_t mix64_host(uint64_t z) { return mix64(z); }
+uint64_t draw_rng_key_host(uint64_t seed, uint64_t epoch) { return draw_rng_key(seed, epoch); }
 
 PermKey make_perm_key(uint64_t n, uint64_t seed, uint64_t epoch) {
     PermKey p{};

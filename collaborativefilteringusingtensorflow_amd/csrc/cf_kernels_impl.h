@@ -62,6 +62,9 @@
 #ifndef CF_PREP_CHUNKS_W1
 #define CF_PREP_CHUNKS_W1 (64 / CF_PREP_GL_W1)   // row chunks in flight at W = 1: one scan covers 64 ids
 #endif
+#ifndef CF_PREP_GL_REC
+#define CF_PREP_GL_REC 1            // lanes per pair in the record draw (prep_recs_body): 1, 2 or 4
+#endif
 #ifndef CF_SORT_MIN_WAVES
 #define CF_SORT_MIN_WAVES 1         // grad_sort_kernel: minimum waves per SIMD (1: the compiler's budget)
 #endif
@@ -437,10 +440,6 @@ __device__ __forceinline__ float softplus(float x) {
     return x > 0.f ? x + log1pf(expf(-x)) : log1pf(expf(x));
 }
 
-__device__ __forceinline__ int32_t draw_item(uint64_t key, uint64_t ctr, int64_t n_items) {
-    return (int32_t)uniform_below(mix64(key + ctr), (uint64_t)n_items);
-}
-
 // ---------------------------------------------------------------------------
 // prep: sample (or load) the batch and count row occurrences
 // ---------------------------------------------------------------------------
@@ -555,7 +554,7 @@ __device__ __forceinline__ void prep_body(const StepArgs& a, int block) {
                                               : a.pairs[permute(slot, a.perm)];
         u = pr.x;
         i = pr.y;
-        key = mix64(a.rng_key ^ (slot * 0xD1B54A32D192ED03ull));
+        key = draw_pair_key(a.rng_key, slot);
         rb = (int64_t)(uint32_t)pr.z;
         re = rb + pr.w;
     } else {
@@ -718,16 +717,51 @@ __device__ __forceinline__ void prep_body(const StepArgs& a, int block) {
     }
 }
 
+// The record draw (StepArgs::neg_recs; W = 1, no group users): the epoch pass
+// drew the pair's negative with the same key and attempt sequence and left it
+// in the record (u, i, j, 0), so nothing here depends on anything but that
+// one coalesced load -- no hashing, no row fetch, no selection.  The three ids
+// are three jobs (user, positive, negative): a returning count atomic each,
+// then the id's and the rank's stores; lane gl of a pair's LPP lanes takes
+// the jobs k = gl, gl + LPP, .. and every atomic is issued before the first
+// store (the rank stores wait for them).
+template <int LPP>
+__device__ __forceinline__ void prep_recs_body(const StepArgs& a, int block) {
+    static_assert(LPP == 1 || LPP == 2 || LPP == 4, "lanes per pair of the record draw");
+    const int gl = threadIdx.x & (LPP - 1);
+    const int p = block * (kBlock / LPP) + (threadIdx.x / LPP);
+    if (p >= a.B) return;
+    const int4 pr = a.order_recs[a.slot_base + (uint64_t)p];
+    const int32_t id[3] = {pr.x, pr.y, pr.z};
+    int32_t* const cnt[3] = {a.cntU, a.cntP != nullptr ? a.cntP : a.cntV, a.cntV};
+    const bool count[3] = {a.count_users != 0, a.count_items != 0, a.count_items != 0};
+    int32_t* const occ[3] = {a.occU + p, a.occV + p, a.occV + a.B + p};
+    int32_t* const rank[3] = {a.rankU + p, a.rankV + p, a.rankV + a.B + p};
+    int32_t rk[3] = {0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        if ((k & (LPP - 1)) == gl && count[k]) rk[k] = atomicAdd(&cnt[k][id[k]], 1);
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        if ((k & (LPP - 1)) == gl) *occ[k] = id[k];
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        if ((k & (LPP - 1)) == gl && count[k]) *rank[k] = rk[k];
+}
+
 // the draw + count of one block of a step's batch
 template <int MODEL>
 __device__ __forceinline__ void prep_any(const StepArgs& a, int block) {
-    if (a.W == 1)
+    if (a.neg_recs)
+        prep_recs_body<CF_PREP_GL_REC>(a, block);
+    else if (a.W == 1)
         prep_body<MODEL, CF_PREP_GL_W1>(a, block);
     else
         prep_body<MODEL>(a, block);
 }
 
 __host__ __device__ __forceinline__ int prep_pairs_per_block(const StepArgs& a) {
+    if (a.neg_recs) return kBlock / CF_PREP_GL_REC;
     return a.W == 1 ? kBlock / CF_PREP_GL_W1 : kPrepPairsPerBlock;
 }
 

@@ -428,8 +428,12 @@ enum cf_path_flag {
     CF_PATH_DETERMINISTIC = 8,  /* sort-based ranks, compact slots, no float atomics       */
     CF_PATH_DENSE_ITEMS = 16,   /* multi-rank item path (dense item gradient)              */
     CF_PATH_LDS = 32,           /* gradient kernel with LDS-staged negatives (grad_lds_kernel) */
-    CF_PATH_SORTED_BATCHES = 64 /* device-sampled batches in CSR order (option "sorted_batches";
+    CF_PATH_SORTED_BATCHES = 64,/* device-sampled batches in CSR order (option "sorted_batches";
                                    auto turns off for good once the orders did not fit in HBM) */
+    CF_PATH_NEG_RECORDS = 128   /* the epoch order's records carry their negatives, the step's
+                                   draw only loads and counts them (option "neg_records": sorted
+                                   batches in the records form on the counting sort, one negative
+                                   per pair, no group users, the row-scan draw)                 */
 };
 int cf_step_path(cf_engine* eng, int32_t B, int32_t* flags_out);
 
@@ -623,6 +627,19 @@ int cf_evaluate(cf_engine* eng, const int32_t* users, int32_t n, const int32_t* 
  *                occurrence whose slot row psort zeroes.  Same batches, same
  *                sums up to fp32 order; 0 (default since round 5's sorted
  *                batches: 3 us faster at cfg2) = count after the scan.
+ *   "neg_records" the epoch order draws the negatives: 0 = off, 1 = on, 2 =
+ *                auto (default; as 1).  Where it applies, the pass that
+ *                sorts an epoch's pair records into batch order also draws
+ *                each pair's negative (same key, same attempt sequence, same
+ *                membership test against the user's CSR row) and writes the
+ *                record as (u, i, j, 0); the step's draw is then the record's
+ *                load and its three count atomics -- no hashing, no row
+ *                fetch.  Same batches bit for bit.  It applies to sorted
+ *                batches in the records form on the counting sort
+ *                ("sorted_batches" 1 / 2, "epoch_sort" 0, at most 1,024 bins)
+ *                with one negative per pair, no group users, "neg_check" 0,
+ *                "spec_neg" 0 and "user_runs" 0; anything else keeps the
+ *                row-scan draw (cf_step_path: CF_PATH_NEG_RECORDS).
  *   "pair_prefetch" accepted at 0 only (any other value is CF_EINVAL).  1
  *                used to make the pos_sort gradient launch fetch the next
  *                step's pair records for its draw; it measured slower at

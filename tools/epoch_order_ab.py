@@ -21,6 +21,9 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--users", type=int, default=1_000_000)
     ap.add_argument("--items", type=int, default=100_000)
+    ap.add_argument("--neg-records", type=int, default=-1,
+                    help="cf_set_option neg_records (records form on the counting sort: the order "
+                         "with the negatives drawn into it); -1 = the engine's default")
     args = ap.parse_args()
     from collaborativefilteringusingtensorflow_amd import _native as N
     from collaborativefilteringusingtensorflow_amd.engine import Engine, synth_graph
@@ -32,6 +35,8 @@ def main():
                 e = Engine("bpr", args.users, args.items, 8, n_neg=1, seed=1)
                 e.set_option("sorted_batches", sb)
                 e.set_option("epoch_sort", es)
+                if args.neg_records >= 0:
+                    e.set_option("neg_records", args.neg_records)
                 e.set_interactions(ip, ix)
                 e.sample(B)   # allocate, first order
                 e.synchronize()
