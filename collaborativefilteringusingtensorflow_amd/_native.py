@@ -20,6 +20,7 @@ AMF_MODES = {"reference": CF_AMF_REFERENCE, "apr": CF_AMF_APR}
 CF_LRML_REFERENCE, CF_LRML_TRAIN = 0, 1
 LRML_MODES = {"reference": CF_LRML_REFERENCE, "train": CF_LRML_TRAIN}
 CF_PW_MF, CF_PW_SVD = 0, 1
+CF_KNN_POP, CF_KNN_USER, CF_KNN_ITEM, CF_KNN_USERITEM = 0, 1, 2, 3
 MODEL_IDS = {"bpr": CF_BPR, "bprmf": CF_BPR, "gbpr": CF_GBPR, "gbprmf": CF_GBPR,
              "cml": CF_CML, "amf": CF_AMF, "plr": CF_PLR, "prigp": CF_PLR, "cplr": CF_PLR}
 TABLES = {"user": 0, "item": 1, "bias": 2, "acc_user": 3, "acc_item": 4, "acc_bias": 5}
@@ -177,6 +178,17 @@ SIGNATURES = {
     "cf_pw_take_loss": (ctypes.c_int, [_P, _PD]),
     "cf_pw_eval": (ctypes.c_int, [_P, _PI32, _PF, _I64, _F, _F, _PF, _PD]),
     "cf_pw_score_topk": (ctypes.c_int, [_P, _PI32, _I32, _I32, _I32, _PI32, _PF]),
+    "cf_knn_create": (ctypes.c_int, [_I64, _I64, _I32, _I32, ctypes.c_double, _I32, ctypes.POINTER(_P)]),
+    "cf_knn_destroy": (ctypes.c_int, [_P]),
+    "cf_knn_set_option": (ctypes.c_int, [_P, ctypes.c_char_p, _I64]),
+    "cf_knn_set_interactions": (ctypes.c_int, [_P, _PI64, _PI32, _I64]),
+    "cf_knn_fit": (ctypes.c_int, [_P]),
+    "cf_knn_get_neighbours": (ctypes.c_int, [_P, _I32, _PI32, _PF]),
+    "cf_knn_set_neighbours": (ctypes.c_int, [_P, _I32, _PI32, _PF]),
+    "cf_knn_check_neighbours": (ctypes.c_int, [_I64, _I32, _PI32, _PF]),
+    "cf_knn_similarity": (ctypes.c_int, [_P, _I32, _PI32, _I32, _PF]),
+    "cf_knn_predict": (ctypes.c_int, [_P, _PI32, _I32, _PD]),
+    "cf_knn_score_topk": (ctypes.c_int, [_P, _PI32, _I32, _I32, _I32, _PI32, _PF]),
     "cf_rating_sampler_create": (ctypes.c_int, [_PI64, _PI32, _PD, _I64, _I64, ctypes.c_double, _I32,
                                                  ctypes.c_uint32, ctypes.POINTER(_P)]),
     "cf_rating_sampler_next": (ctypes.c_int, [_P, _PI32, _PF]),

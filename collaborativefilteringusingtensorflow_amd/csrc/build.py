@@ -23,7 +23,7 @@ LIB = os.path.join(OUT, "libcf_engine.so")
 SOURCES = ["cf_grad_bpr.hip", "cf_grad_amf.hip", "cf_grad_cml.hip", "cf_grad_gbpr.hip", "cf_grad_plr.hip",
            "cf_kernels.hip", "cf_eval.hip", "cf_metrics.hip", "cf_engine.cpp", "cf_synth.cpp", "cf_ingest.cpp",
            "cf_mt_sampler.cpp", "cf_ensemble.hip", "cf_det.hip", "cf_epoch.hip", "cf_lrml.hip",
-           "cf_pointwise.hip"]
+           "cf_pointwise.hip", "cf_knn.hip"]
 HEADERS = ["cf_kernels.h", "cf_device.h", "cf_kernels_impl.h", "cf_host.h",
            os.path.join(ROOT, "include", "cf_engine.h")]
 ARCH = os.environ.get("CF_OFFLOAD_ARCH", "gfx950")

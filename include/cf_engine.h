@@ -864,6 +864,51 @@ int cf_pw_eval(cf_pw* e, const int32_t* host_ui, const float* host_r, int64_t n,
 int cf_pw_score_topk(cf_pw* e, const int32_t* host_users, int32_t n, int32_t k, int32_t exclude_train,
                      int32_t* host_idx_out, float* host_val_out);
 
+/* ---- the neighbourhood family: PopRank, UserCF, ItemCF, UserItemCF -------------
+ * src/models/basic/models/pop.py, usercf.py, itemcf.py and
+ * src/models/others/models/useritemcf.py on the binarised train matrix (a
+ * pattern-only CSR).  Similarity of rows a != b of a side with c common members:
+ * S[a,b] = fl32(fl32(c / den_lo) / den_hi), den_x = float32(sqrt(nnz_x)), lo =
+ * min(a,b), hi = max(a,b) -- the bits of usercf.py:19-27; the diagonal and rows
+ * without members are 0.  Neighbours of a row: its topK largest positive
+ * similarities, sorted by descending similarity, ties to the lower id, padded
+ * with (-1, 0).  Predictions are float64 sums of float32 terms: UserCF
+ * sum_{v in N(u)} S[u,v] R[v,:]; ItemCF sum_{i in R_u} Sk[i,:]; UserItemCF both,
+ * the terms fl32(fl32(theta) S_user) and fl32(fl32(1. - theta) S_item); PopRank
+ * the item's train count.  Sides: 0 users, 1 items.  No sum takes an atomic and
+ * every order is fixed: equal inputs give equal bytes. */
+typedef struct cf_knn cf_knn;
+enum {
+    CF_KNN_POP = 0,       /* pop.py        */
+    CF_KNN_USER = 1,      /* usercf.py     */
+    CF_KNN_ITEM = 2,      /* itemcf.py     */
+    CF_KNN_USERITEM = 3   /* useritemcf.py */
+};
+/* topK 1..4096, theta in [0,1] (checked for every kind; UserItemCF alone reads theta) */
+int cf_knn_create(int64_t n_users, int64_t n_items, int32_t kind, int32_t topK, double theta,
+                  int32_t device, cf_knn** out);
+int cf_knn_destroy(cf_knn* e);
+/* "tile_cols" (similarity pass, u32 counts, <= 16384) and "tile_items" (prediction
+ * pass, fp64 sums, <= 8192): the LDS tile widths; 0 = the default */
+int cf_knn_set_option(cf_knn* e, const char* name, int64_t value);
+/* the train CSR (sorted rows); the object builds the transpose and the norms */
+int cf_knn_set_interactions(cf_knn* e, const int64_t* indptr, const int32_t* indices, int64_t nnz);
+/* builds the [n_side, topK] neighbour tables the kind reads (PopRank: none) */
+int cf_knn_fit(cf_knn* e);
+/* a side's table: ids int32 and similarities float32, [n_side, topK] each */
+int cf_knn_get_neighbours(cf_knn* e, int32_t side, int32_t* host_idx_out, float* host_sim_out);
+/* replaces it; ids are -1 (a pad) or in range, no id twice in a row, similarities finite */
+int cf_knn_set_neighbours(cf_knn* e, int32_t side, const int32_t* host_idx, const float* host_sim);
+/* the setter's check alone (host only, needs no object) */
+int cf_knn_check_neighbours(int64_t n_side, int32_t topK, const int32_t* host_idx, const float* host_sim);
+/* dense similarity rows of either side, for any kind: out [n, n_side] float32 */
+int cf_knn_similarity(cf_knn* e, int32_t side, const int32_t* host_rows, int32_t n, float* host_out);
+/* dense predictions: out [n, n_items] float64 */
+int cf_knn_predict(cf_knn* e, const int32_t* host_users, int32_t n, double* host_out);
+/* top-k of float32(prediction) with the exclude / tie rules of cf_score_topk */
+int cf_knn_score_topk(cf_knn* e, const int32_t* host_users, int32_t n, int32_t k, int32_t exclude_train,
+                      int32_t* host_idx_out, float* host_val_out);
+
 /* ---- sampler_rating, bit-exact (host) ------------------------------------------
  * src/samplers/sampler_rating.py:22-39 for np.random.seed(seed) set right
  * before the sampler is built: the (user, item, rating) tuples in nonzero()
